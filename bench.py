@@ -28,11 +28,21 @@ aggregate. ``--parallel tp`` instead shards ONE engine across all ranks
 and scheduler, other ranks follow in lockstep (parallel/serve.py).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+                       [--dump-outputs DIR] [--full]
 Rank 0 prints exactly one JSON result line.
+
+A plain run does only what the headline figure needs: build the engine, warm
+up, time the K steps, print the line. ``--dump-outputs DIR`` additionally
+writes what the LAST timed step returned to its callers (see dump_outputs)
+so two builds can be compared output for output; prompts, request seeds and
+weight-init seed depend only on the arguments. ``--full`` is where any
+measurement beyond the headline belongs (baselines, other configs, per-kernel
+figures); the benchmark has none today, so it currently adds nothing.
 """
 
 import argparse
 import asyncio
+import contextlib
 import json
 import os
 import sys
@@ -56,9 +66,8 @@ def log(msg):
         print(msg, file=sys.stderr, flush=True)
 
 
-def _mean_likelihood(node) -> float:
-    """Average of all leaf confidences — the reference's 'consensus quality'
-    scale (README_TESTS.md:269-273: 0.8-0.9 good)."""
+def _likelihood_leaves(node) -> list:
+    """Leaf confidences in traversal order (dict insertion / list order)."""
     leaves = []
 
     def walk(v):
@@ -72,6 +81,13 @@ def _mean_likelihood(node) -> float:
             leaves.append(float(v))
 
     walk(node)
+    return leaves
+
+
+def _mean_likelihood(node) -> float:
+    """Average of all leaf confidences — the reference's 'consensus quality'
+    scale (README_TESTS.md:269-273: 0.8-0.9 good)."""
+    leaves = _likelihood_leaves(node)
     return sum(leaves) / len(leaves) if leaves else 0.0
 
 
@@ -106,6 +122,63 @@ def _enable_tunableop(local_rank: int) -> None:
             atexit.register(lambda: log(f"[bench] tuned results in {tmp}"))
     except Exception as e:
         log(f"[bench] tunableop disabled ({e})")
+
+
+def dump_outputs(out_dir: str, responses: list) -> None:
+    """Write what the last timed step's create()/parse() calls returned, one
+    row per request in request order, as float .npy arrays (padding = -1):
+
+      content.npy      float32 [batch, n+1, L]  UTF-8 bytes of every choice's
+                       message content (choice 0 = consensus, 1.. = originals)
+      content_len.npy  float32 [batch, n+1]     byte length of each content
+      likelihoods.npy  float64 [batch, K]       leaf confidences, traversal order
+      usage.npy        float64 [batch, 3]       prompt/completion/total tokens
+
+    A step is batch*(n+1) short strings, so the whole dump is far below a MB.
+    """
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    texts = [[(ch.message.content or "").encode("utf-8") for ch in r.choices]
+             for r in responses]
+    n_choices = max((len(row) for row in texts), default=0)
+    width = max((len(t) for row in texts for t in row), default=0)
+    content = np.full((len(texts), n_choices, max(1, width)), -1.0, dtype=np.float32)
+    content_len = np.full((len(texts), n_choices), -1.0, dtype=np.float32)
+    for i, row in enumerate(texts):
+        for j, t in enumerate(row):
+            content[i, j, :len(t)] = np.frombuffer(t, dtype=np.uint8)
+            content_len[i, j] = len(t)
+    leaves = [_likelihood_leaves(r.likelihoods) for r in responses]
+    k_max = max((len(l) for l in leaves), default=0)
+    lik = np.full((len(leaves), max(1, k_max)), -1.0, dtype=np.float64)
+    for i, l in enumerate(leaves):
+        lik[i, :len(l)] = l
+    usage = np.array(
+        [[r.usage.prompt_tokens, r.usage.completion_tokens, r.usage.total_tokens]
+         if r.usage is not None else [-1, -1, -1] for r in responses],
+        dtype=np.float64).reshape(len(responses), 3)
+    np.save(os.path.join(out_dir, "content.npy"), content)
+    np.save(os.path.join(out_dir, "content_len.npy"), content_len)
+    np.save(os.path.join(out_dir, "likelihoods.npy"), lik)
+    np.save(os.path.join(out_dir, "usage.npy"), usage)
+
+
+@contextlib.contextmanager
+def _skip_default_param_init():
+    """Setup-time only: the engine overwrites EVERY parameter right after it
+    constructs the modules (seeded random init, or a checkpoint), so torch's
+    default nn.Embedding / nn.Linear initialisers — ~1 G elements drawn on the
+    CPU for the 8B vocab matrices, most of the engine build time — are wasted
+    work. Make them no-ops while the engine is built; the weights the timed
+    steps run on are unchanged."""
+    init = torch.nn.init
+    saved = init.normal_, init.kaiming_uniform_
+    init.normal_ = init.kaiming_uniform_ = lambda tensor, *a, **kw: tensor
+    try:
+        yield
+    finally:
+        init.normal_, init.kaiming_uniform_ = saved
 
 
 def make_prompt(rank: int, step: int, i: int, prompt_len_tokens: int) -> str:
@@ -166,6 +239,10 @@ def main():
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--parallel", type=str, default="dp", choices=["dp", "tp"],
                     help="dp: one engine per rank (weak scaling); tp: ONE engine sharded over all ranks")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's responses as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run measurements beyond the headline figure (none today)")
     args = ap.parse_args()
 
     cfgd = CONFIG_DEFAULTS[args.config]
@@ -220,7 +297,8 @@ def main():
         from kllms_amd.parallel.serve import TPFollower
 
         eng_client = LocalEngineClient(**client_kwargs)
-        follower = TPFollower(eng_client.engine)
+        with _skip_default_param_init():
+            follower = TPFollower(eng_client.engine)
         log(f"[bench] rank {rank}: follower ready in {time.perf_counter() - t_build:.1f}s")
         follower.run()  # blocks until rank 0 sends stop
         if dist is not None:
@@ -230,7 +308,8 @@ def main():
 
     k = AsyncKLLMs(**client_kwargs)
     eng_client = k.client
-    _ = eng_client.engine  # materialize weights now
+    with _skip_default_param_init():
+        _ = eng_client.engine  # materialize weights now
     if tp_mode:
         from kllms_amd.parallel.serve import TPCoordinator
 
@@ -262,11 +341,12 @@ def main():
         return res
 
     prev_stats = {}
+    last_responses: list = []
 
     async def run_step(step_idx: int):
         import time as _t
         t0 = _t.perf_counter()
-        await asyncio.gather(*(one_request(step_idx, i) for i in range(batch)))
+        last_responses[:] = await asyncio.gather(*(one_request(step_idx, i) for i in range(batch)))
         if os.environ.get("KLLMS_BENCH_VERBOSE"):
             sched = getattr(eng_client, "_scheduler", None)
             cur = dict(sched.stats) if sched else {}
@@ -309,6 +389,9 @@ def main():
                          device=device if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, last_responses)
 
     n_engines = 1 if tp_mode else world_size
     total_requests = args.steps * batch * n_engines

@@ -1,332 +1,195 @@
 """Differential tests against the REFERENCE implementation itself.
 
-When the reference snapshot is mounted (at /root/reference, as in the build
-environment), import its consensus machinery with its third-party
-dependencies stubbed by our own pure-python equivalents, and fuzz BOTH
-implementations on the same inputs. This checks parity directly against the
-reference's code rather than against a re-derivation of its behavior.
+tests/golden/reference_differential.json.gz holds, per property, a fixed
+seeded set of hypothesis-drawn inputs with what the reference's own
+consensus/alignment/consolidation code returned for each (or the exception it
+raised); scripts/record_reference_goldens.py recorded it from a reference
+checkout. Each test runs THIS implementation on the same inputs and asserts
+exact agreement — parity against the reference's code, not a re-derivation,
+without needing the reference to run the suite.
 
-Stubs (the reference's imports that are not installed here):
-- Levenshtein.distance      -> kllms_amd.utils.text.levenshtein_distance
-- unidecode.unidecode       -> kllms_amd.utils.text.ascii_transliterate
-- cachetools.TTLCache       -> dict subclass (ttl ignored; deterministic)
-- openai / retab            -> inert stubs (only llm-consensus + usage
-                               summation touch them; not exercised here)
-
-Skipped automatically when the snapshot is absent (e.g. on a GPU box).
+Where the reference crashed, only its documented crash classes may be
+skipped (hardened divergences, docs/PARITY.md); the entry points with crash
+parity must raise the same exception type.
 """
 
-import importlib.util
+import asyncio
+import gzip
+import importlib
+import json
 import math
 import os
-import sys
-import types
+import random
 
 import pytest
 
-REF_UTILS = "/root/reference/k_llms/utils"
-if not os.path.isdir(REF_UTILS):
-    pytest.skip("reference snapshot not mounted", allow_module_level=True)
-
-hypothesis = pytest.importorskip("hypothesis")
-from hypothesis import HealthCheck, given, settings, strategies as st  # noqa: E402
-
-from kllms_amd.consensus import (  # noqa: E402
+from kllms_amd.consensus import (
     ConsensusSettings,
     consensus_values,
     lists_alignment,
+    low_cutoff_bound,
     recursive_list_alignments,
+    remove_outliers,
+    sort_by_original_majority,
 )
-from kllms_amd.consensus.similarity import generic_similarity  # noqa: E402
-from kllms_amd.utils.text import ascii_transliterate, levenshtein_distance  # noqa: E402
+from kllms_amd.consensus import fuzzy_key_selection, key_selection
+from kllms_amd.consensus.aio import async_consolidate_chat_completions
+from kllms_amd.consensus.consolidation import consolidate_chat_completions
+from kllms_amd.consensus.key_based_alignment import recursive_align
+from kllms_amd.consensus.similarity import (
+    compute_similarity_scores,
+    generic_similarity,
+    normalize_string,
+    numerical_similarity,
+    sanitize_value,
+)
+from kllms_amd.consensus.values import intermediary_consensus_cleanup
 
-
-# ---------------------------------------------------------------------------
-# Load the reference module with stubbed dependencies
-# ---------------------------------------------------------------------------
-
-def _stub(name, **attrs):
-    m = types.ModuleType(name)
-    for k, v in attrs.items():
-        setattr(m, k, v)
-    sys.modules.setdefault(name, m)
-    return sys.modules[name]
-
-
-class _TTLCacheStub(dict):
-    def __init__(self, maxsize=1024, ttl=300):
-        super().__init__()
-        self.maxsize = maxsize
-        self.ttl = ttl
-
-    def __setitem__(self, k, v):
-        if len(self) >= self.maxsize:
-            self.clear()
-        super().__setitem__(k, v)
+GOLDEN_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                           "golden", "reference_differential.json.gz")
 
 
 @pytest.fixture(scope="module")
-def ref():
-    _stub("Levenshtein", distance=levenshtein_distance)
-    _stub("unidecode", unidecode=ascii_transliterate)
-    _stub("cachetools", TTLCache=_TTLCacheStub)
-    _stub("openai", OpenAI=type("OpenAI", (), {}), AsyncOpenAI=type("AsyncOpenAI", (), {}))
-    _stub("openai.types")
-    _stub(
-        "openai.types.completion_usage",
-        CompletionUsage=type("CompletionUsage", (), {}),
-        CompletionTokensDetails=type("CompletionTokensDetails", (), {}),
-        PromptTokensDetails=type("PromptTokensDetails", (), {}),
-    )
-    _stub("retab")
-    _stub("retab.types")
-    _stub("retab.types.documents")
-    _stub("retab.types.documents.extract", RetabParsedChatCompletion=type("RetabParsedChatCompletion", (), {}))
-
-    pkg = types.ModuleType("_refk")
-    pkg.__path__ = [REF_UTILS]
-    sys.modules.setdefault("_refk", pkg)
-    for sub in ("majority_sorting", "consensus_utils"):
-        spec = importlib.util.spec_from_file_location(
-            f"_refk.{sub}", os.path.join(REF_UTILS, f"{sub}.py")
-        )
-        mod = importlib.util.module_from_spec(spec)
-        sys.modules[f"_refk.{sub}"] = mod
-        spec.loader.exec_module(mod)
-    return sys.modules["_refk.consensus_utils"]
+def golden():
+    with gzip.open(GOLDEN_PATH, "rt") as f:
+        return json.load(f)
 
 
-def _assert_known_ref_crash(e):
+def _hashable(v):
+    return tuple(_hashable(x) for x in v) if isinstance(v, list) else v
+
+
+def _dec(v):
+    """Inverse of the recorder's encoding: {"__items__": [[k, v], ...]} is a
+    dict with non-string keys; everything else is plain JSON."""
+    if isinstance(v, dict):
+        if set(v) == {"__items__"}:
+            return {_hashable(_dec(k)): _dec(x) for k, x in v["__items__"]}
+        return {k: _dec(x) for k, x in v.items()}
+    if isinstance(v, list):
+        return [_dec(x) for x in v]
+    return v
+
+
+def _deep_eq(a, b, path="", tol=1e-9):
+    if isinstance(a, float) and isinstance(b, float):
+        assert (math.isnan(a) and math.isnan(b)) or a == pytest.approx(b, abs=tol), f"{path}: {a} != {b}"
+        return
+    if isinstance(a, dict) and isinstance(b, dict):
+        assert set(a) == set(b), f"{path}: keys {set(a)} != {set(b)}"
+        for k in a:
+            _deep_eq(a[k], b[k], f"{path}.{k}", tol)
+        return
+    if isinstance(a, (list, tuple)) and isinstance(b, (list, tuple)):
+        assert len(a) == len(b), f"{path}: len {len(a)} != {len(b)}"
+        for i, (x, y) in enumerate(zip(a, b)):
+            _deep_eq(x, y, f"{path}[{i}]", tol)
+        return
+    assert a == b, f"{path}: {a!r} != {b!r}"
+
+
+def _approx(tol):
+    def check(got, want, label):
+        assert got == pytest.approx(want, abs=tol), label
+    return check
+
+
+def _known_ref_crash(crash, _rerun):
     """Only the documented reference crash classes may be skipped; anything
-    else means the harness itself miscalled the reference (which would make
-    every comparison silently vacuous)."""
-    msg = f"{type(e).__name__}: {e}"
+    else means the recording miscalled the reference (which would make every
+    comparison silently vacuous)."""
+    msg = crash["msg"]
     known = (
-        "unhashable" in str(e)                      # Counter on list/dict votes
-        or "has no len()" in str(e)                 # key-aligner None-mixed lists
-        or "'<' not supported" in str(e)            # key-aligner mixed-type key sort
-        or isinstance(e, RecursionError)
+        "unhashable" in msg                      # Counter on list/dict votes
+        or "has no len()" in msg                 # key-aligner None-mixed lists
+        or "'<' not supported" in msg            # key-aligner mixed-type key sort
+        or crash["type"] == "builtins.RecursionError"
     )
-    assert known, f"unexpected reference crash treated as divergence: {msg}"
+    assert known, f"unexpected reference crash treated as divergence: {crash['type']}: {msg}"
+
+
+def _same_crash(crash, rerun):
+    """Crash parity: ours must fail with the SAME exception type (e.g.
+    all-empty contents -> likelihoods=1.0 -> pydantic rejects; ValueError
+    "No extractions" / "No scalar candidate paths" in key selection)."""
+    mod, _, qual = crash["type"].rpartition(".")
+    with pytest.raises(getattr(importlib.import_module(mod), qual)):
+        rerun()
+
+
+def _same_crash_unless_unhashable(crash, rerun):
+    if "unhashable" not in crash["msg"]:   # documented hardening divergence
+        _same_crash(crash, rerun)
+
+
+def _replay(golden, name, n_cases, ours, check=_deep_eq, on_crash=_known_ref_crash):
+    """Run ours(input) on every recorded case of property `name` (at least
+    n_cases, the count the property was fuzzed at — a truncated recording
+    must not pass) and compare with the reference's recorded result."""
+    cases = golden[name]
+    assert len(cases) >= n_cases, f"{name}: {len(cases)} recorded cases < {n_cases}"
+    for i, c in enumerate(cases):
+        x = json.loads(json.dumps(c["in"]))   # fresh copy per case
+        if "crash" in c:
+            on_crash(c["crash"], lambda: ours(x))
+        else:
+            check(ours(x), _dec(c["want"]), f"{name} case {i}: {c['in']!r}")
 
 
 def fake_embed(texts):
     return [[float(len(t) % 7) + 0.25, float(sum(map(ord, t)) % 11), 1.0] for t in texts]
 
 
-def _deep_eq(a, b, path=""):
-    if isinstance(a, float) and isinstance(b, float):
-        assert (math.isnan(a) and math.isnan(b)) or a == pytest.approx(b, abs=1e-9), f"{path}: {a} != {b}"
-        return
-    if isinstance(a, dict) and isinstance(b, dict):
-        assert set(a) == set(b), f"{path}: keys {set(a)} != {set(b)}"
-        for k in a:
-            _deep_eq(a[k], b[k], f"{path}.{k}")
-        return
-    if isinstance(a, (list, tuple)) and isinstance(b, (list, tuple)):
-        assert len(a) == len(b), f"{path}: len {len(a)} != {len(b)}"
-        for i, (x, y) in enumerate(zip(a, b)):
-            _deep_eq(x, y, f"{path}[{i}]")
-        return
-    assert a == b, f"{path}: {a!r} != {b!r}"
+def _lev():
+    return ConsensusSettings(string_similarity_method="levenshtein")
 
 
-# strategies: ASCII-restricted so the transliteration stub is exercised
-# identically on both sides
-ascii_text = st.text(
-    alphabet=st.characters(min_codepoint=0x20, max_codepoint=0x7E), max_size=14
-)
-scalars = st.one_of(
-    st.none(),
-    st.booleans(),
-    st.integers(min_value=-10**6, max_value=10**6),
-    st.floats(allow_nan=False, allow_infinity=False, width=32),
-    ascii_text,
-)
-json_values = st.recursive(
-    scalars,
-    lambda ch: st.one_of(
-        st.lists(ch, max_size=3),
-        st.dictionaries(st.sampled_from(["a", "b", "k1", "k2", "name"]), ch, max_size=3),
-    ),
-    max_leaves=8,
-)
+def test_generic_similarity_matches_reference(golden):
+    _replay(golden, "generic_similarity", 150,
+            lambda x: generic_similarity(x[0], x[1], "levenshtein", fake_embed), check=_approx(1e-9))
 
 
-# KLLMS_FUZZ_DEEP=<mult> scales every property's example count for long
-# validation campaigns (the explicit @settings below absorb the multiplier)
-_DEEP = max(1, int(os.environ.get("KLLMS_FUZZ_DEEP", "1")))
-
-@settings(max_examples=_DEEP * 150, deadline=None, suppress_health_check=[HealthCheck.too_slow])
-@given(json_values, json_values)
-def test_generic_similarity_matches_reference(ref, a, b):
-    ours = generic_similarity(a, b, "levenshtein", fake_embed)
-    theirs = ref.generic_similarity(a, b, "levenshtein", fake_embed)
-    assert ours == pytest.approx(theirs, abs=1e-9), f"{a!r} vs {b!r}"
+def test_consensus_values_matches_reference(golden):
+    _replay(golden, "consensus_values", 120, lambda v: consensus_values(v, _lev(), fake_embed))
 
 
-@settings(max_examples=_DEEP * 120, deadline=None, suppress_health_check=[HealthCheck.too_slow])
-@given(st.lists(json_values, min_size=1, max_size=5))
-def test_consensus_values_matches_reference(ref, values):
-    ours_settings = ConsensusSettings(string_similarity_method="levenshtein")
-    ref_settings = ref.ConsensusSettings(string_similarity_method="levenshtein")
-    try:
-        want_val, want_conf = ref.consensus_values(list(values), ref_settings, fake_embed, None)
-    except Exception as e:
-        # reference crashes (e.g. unhashable vote in a bool field) — our
-        # hardened path diverges deliberately there (docs/PARITY.md). Any
-        # OTHER crash class would mean the harness is miscalling the ref.
-        _assert_known_ref_crash(e)
-        return
-    got_val, got_conf = consensus_values(list(values), ours_settings, fake_embed)
-    _deep_eq(got_val, want_val, "value")
-    _deep_eq(got_conf, want_conf, "confidence")
+def test_recursive_alignment_matches_reference(golden):
+    _replay(golden, "recursive_alignment", 80,
+            lambda v: recursive_list_alignments(v, "levenshtein", fake_embed, None, 0.51))
 
 
-@settings(max_examples=_DEEP * 80, deadline=None, suppress_health_check=[HealthCheck.too_slow])
-@given(st.lists(json_values, min_size=2, max_size=4))
-def test_recursive_alignment_matches_reference(ref, values):
-    try:
-        want, want_km = ref.recursive_list_alignments(
-            list(values), "levenshtein", fake_embed, None, 0.51
-        )
-    except Exception as e:
-        _assert_known_ref_crash(e)
-        return
-    got, got_km = recursive_list_alignments(list(values), "levenshtein", fake_embed, None, 0.51)
-    _deep_eq(got, want, "aligned")
-    _deep_eq(got_km, want_km, "key_mappings")
-
-
-@settings(max_examples=_DEEP * 80, deadline=None, suppress_health_check=[HealthCheck.too_slow])
-@given(st.lists(st.lists(ascii_text, max_size=4), min_size=2, max_size=4))
-def test_lists_alignment_matches_reference(ref, lists):
-    def ours_sim(a, b):
+def test_lists_alignment_matches_reference(golden):
+    def sim(a, b):
         return generic_similarity(a, b, "levenshtein", fake_embed)
 
-    def ref_sim(a, b):
-        return ref.generic_similarity(a, b, "levenshtein", fake_embed)
-
-    try:
-        want, want_idx = ref.lists_alignment(
-            [list(l) for l in lists], ref_sim, None, min_support_ratio=0.51
-        )
-    except Exception as e:
-        _assert_known_ref_crash(e)
-        return
-    got, got_idx = lists_alignment([list(l) for l in lists], ours_sim, min_support_ratio=0.51)
-    _deep_eq(got, want, "aligned")
-    _deep_eq(got_idx, want_idx, "orig_idx")
+    _replay(golden, "lists_alignment", 80, lambda v: lists_alignment(v, sim, min_support_ratio=0.51))
 
 
-# targeted distributions for rarely-hit branches ----------------------------
-
-_centers = st.sampled_from([0.0, 1.0, -1.0, 10.0, 0.001, -1000.0, 1e6])
-_jitter = st.floats(min_value=-0.05, max_value=0.05, allow_nan=False)
-clustered_numbers = st.lists(
-    st.one_of(
-        st.tuples(_centers, _jitter).map(lambda t: t[0] * (1.0 + t[1])),
-        st.tuples(_centers, _jitter).map(lambda t: t[0] * (1.0 + t[1]) * 10.0),   # power-of-10 twins
-        st.tuples(_centers, _jitter).map(lambda t: -t[0] * (1.0 + t[1])),         # signless twins
-        st.none(),
-        st.integers(min_value=-5, max_value=5),
-    ),
-    min_size=2, max_size=7,
-)
-
-
-@settings(max_examples=_DEEP * 200, deadline=None, suppress_health_check=[HealthCheck.too_slow])
-@given(clustered_numbers)
-def test_numeric_consensus_matches_reference(ref, values):
+def test_numeric_consensus_matches_reference(golden):
     """Hybrid numeric clustering incl. tie-breaks by cross-cluster support,
-    signless and power-of-10 equivalence (ref :1127-1219)."""
-    try:
-        want = ref.consensus_values(list(values), ref.ConsensusSettings(), fake_embed, None)
-    except Exception as e:
-        _assert_known_ref_crash(e)
-        return
-    got = consensus_values(list(values), ConsensusSettings(), fake_embed)
-    _deep_eq(got[0], want[0], "value")
-    _deep_eq(got[1], want[1], "confidence")
+    signless and power-of-10 equivalence (ref :1127-1219), on clustered
+    number lists with power-of-10 / signless twins."""
+    _replay(golden, "numeric_consensus", 200,
+            lambda v: consensus_values(v, ConsensusSettings(), fake_embed))
 
 
-@settings(max_examples=_DEEP * 150, deadline=None, suppress_health_check=[HealthCheck.too_slow])
-@given(json_values, json_values, st.sampled_from(["jaccard", "hamming", "embeddings"]))
-def test_similarity_methods_match_reference(ref, a, b, method):
+def test_similarity_methods_match_reference(golden):
     """All four string-similarity methods, incl. the >50-char embeddings gate
     falling back to levenshtein below it (ref :797-824)."""
-    ours = generic_similarity(a, b, method, fake_embed)
-    theirs = ref.generic_similarity(a, b, method, fake_embed)
-    assert ours == pytest.approx(theirs, abs=1e-9), f"{method}: {a!r} vs {b!r}"
+    _replay(golden, "similarity_methods", 150,
+            lambda x: generic_similarity(x[0], x[1], x[2], fake_embed), check=_approx(1e-9))
 
 
-@settings(max_examples=_DEEP * 60, deadline=None, suppress_health_check=[HealthCheck.too_slow])
-@given(st.lists(st.text(alphabet="abcdefgh ", min_size=45, max_size=70), min_size=2, max_size=4))
-def test_long_string_embeddings_consensus_matches_reference(ref, values):
+def test_long_string_embeddings_consensus_matches_reference(golden):
     """string_consensus 'centroid' on long strings routes through the
     embeddings medoid on both sides (same injected embedder)."""
-    s_ours = ConsensusSettings()          # embeddings + centroid defaults
-    s_ref = ref.ConsensusSettings()
-    try:
-        want = ref.consensus_values(list(values), s_ref, fake_embed, None)
-    except Exception as e:
-        _assert_known_ref_crash(e)
-        return
-    got = consensus_values(list(values), s_ours, fake_embed)
-    _deep_eq(got[0], want[0], "value")
-    _deep_eq(got[1], want[1], "confidence")
+    _replay(golden, "long_string_embeddings_consensus", 60,
+            lambda v: consensus_values(v, ConsensusSettings(), fake_embed))
 
 
 # ---------------------------------------------------------------------------
 # Full consolidation differential (the reference's §3.1 entry point)
 # ---------------------------------------------------------------------------
-
-@pytest.fixture(scope="module")
-def ref_consolidation(ref):
-    """Load the reference's consolidation.py with openai CHAT types stubbed by
-    this repo's pydantic-compatible re-declarations, so the reference code
-    runs on the same objects our implementation consumes."""
-    from typing import TypeVar
-
-    from kllms_amd.types import openai_compat as oc
-
-    chat = _stub("openai.types.chat",
-                 ChatCompletion=oc.ChatCompletion,
-                 ParsedChatCompletion=oc.ParsedChatCompletion,
-                 ChatCompletionMessage=oc.ChatCompletionMessage)
-    _stub("openai.types.chat.chat_completion", Choice=oc.Choice)
-    _stub("openai.types.chat.parsed_chat_completion",
-          ParsedChoice=oc.ParsedChoice,
-          ParsedChatCompletionMessage=oc.ParsedChatCompletionMessage)
-    _stub("openai.lib")
-    _stub("openai.lib._parsing", ResponseFormatT=TypeVar("ResponseFormatT"))
-    sys.modules["openai"].types = sys.modules.get("openai.types")
-    if sys.modules.get("openai.types") is not None:
-        sys.modules["openai.types"].chat = chat
-
-    root = types.ModuleType("_refpkg")
-    root.__path__ = ["/root/reference/k_llms"]
-    sys.modules.setdefault("_refpkg", root)
-    tp = types.ModuleType("_refpkg.types")
-    tp.__path__ = ["/root/reference/k_llms/types"]
-    sys.modules.setdefault("_refpkg.types", tp)
-    ut = types.ModuleType("_refpkg.utils")
-    ut.__path__ = [REF_UTILS]
-    sys.modules.setdefault("_refpkg.utils", ut)
-    # reuse the already-loaded flat modules for the relative imports
-    sys.modules.setdefault("_refpkg.utils.majority_sorting", sys.modules["_refk.majority_sorting"])
-    sys.modules.setdefault("_refpkg.utils.consensus_utils", sys.modules["_refk.consensus_utils"])
-    for name, path in (
-        ("_refpkg.types.completions", "/root/reference/k_llms/types/completions.py"),
-        ("_refpkg.types.parsed", "/root/reference/k_llms/types/parsed.py"),
-        ("_refpkg.utils.consolidation", os.path.join(REF_UTILS, "consolidation.py")),
-    ):
-        spec = importlib.util.spec_from_file_location(name, path)
-        mod = importlib.util.module_from_spec(spec)
-        sys.modules[name] = mod
-        spec.loader.exec_module(mod)
-    return sys.modules["_refpkg.utils.consolidation"]
-
 
 def _mk_completion(contents):
     from kllms_amd.types.openai_compat import (
@@ -347,43 +210,21 @@ def _mk_completion(contents):
     )
 
 
-content_strings = st.one_of(
-    json_values.map(lambda v: __import__("json").dumps(v)),   # JSON contents
-    ascii_text,                                               # free text -> {"text": ...}
-)
+def _completion_eq(got, want, label):
+    """want: the recorded summary of a reference completion — choices as
+    [index, finish_reason, content], likelihoods, usage dump."""
+    assert [[g.index, g.finish_reason, g.message.content] for g in got.choices] == want["choices"], label
+    _deep_eq(got.likelihoods, want["likelihoods"], f"{label} likelihoods")
+    assert got.usage.model_dump() == want["usage"], label
 
 
-@settings(max_examples=_DEEP * 100, deadline=None, suppress_health_check=[HealthCheck.too_slow])
-@given(st.lists(content_strings, min_size=1, max_size=5))
-def test_consolidate_chat_completions_matches_reference(ref_consolidation, contents):
-    from kllms_amd.consensus.consolidation import consolidate_chat_completions
-
-    try:
-        want = ref_consolidation.consolidate_chat_completions(
-            _mk_completion(list(contents)), fake_embed, None
-        )
-    except Exception as e:
-        if "unhashable" in str(e):
-            return  # documented hardening divergence
-        # crash parity: ours must fail with the SAME exception type
-        # (e.g. all-empty contents -> likelihoods=1.0 -> pydantic rejects,
-        # in the reference and here alike)
-        with pytest.raises(type(e)):
-            consolidate_chat_completions(_mk_completion(list(contents)), fake_embed)
-        return
-    got = consolidate_chat_completions(_mk_completion(list(contents)), fake_embed)
-    assert len(got.choices) == len(want.choices)
-    for g, w in zip(got.choices, want.choices):
-        assert g.index == w.index
-        assert g.finish_reason == w.finish_reason
-        assert g.message.content == w.message.content, f"choice {g.index}"
-    _deep_eq(got.likelihoods, want.likelihoods, "likelihoods")
-    assert got.usage.model_dump() == want.usage.model_dump()
+def test_consolidate_chat_completions_matches_reference(golden):
+    _replay(golden, "consolidate_chat_completions", 100,
+            lambda c: consolidate_chat_completions(_mk_completion(c), fake_embed),
+            check=_completion_eq, on_crash=_same_crash_unless_unhashable)
 
 
-@settings(max_examples=_DEEP * 60, deadline=None, suppress_health_check=[HealthCheck.too_slow])
-@given(st.lists(content_strings, min_size=1, max_size=4))
-def test_async_consolidation_matches_reference(ref_consolidation, contents):
+def test_async_consolidation_matches_reference(golden):
     """The reference's ASYNC consolidation is hand-duplicated code (not a
     bridge) and has genuinely drifted from its own sync path on bool/number
     mixtures (e.g. contents 0 vs false: sync -> numeric consensus 0.0 at
@@ -391,210 +232,96 @@ def test_async_consolidation_matches_reference(ref_consolidation, contents):
     shared impl bridged to async, so it matches the reference's SYNC
     behavior everywhere — asserted here; where the reference's async agrees
     with its sync, ours must match it too (docs/PARITY.md)."""
-    import asyncio
-
-    from kllms_amd.consensus.aio import async_consolidate_chat_completions
-
     async def aembed(texts):
         return fake_embed(texts)
 
-    async def run_ref():
-        return await ref_consolidation.async_consolidate_chat_completions(
-            _mk_completion(list(contents)), aembed, None
-        )
+    def check(got, want, label):
+        sync, asyn = want["sync"], want["async"]
+        _completion_eq(got, sync, f"{label} (sync)")   # ours always equals the reference's SYNC behavior
+        # and equals the async result wherever the reference hasn't drifted
+        if ([c[2] for c in asyn["choices"]] == [c[2] for c in sync["choices"]]
+                and asyn["likelihoods"] == sync["likelihoods"]):
+            assert [g.message.content for g in got.choices] == [c[2] for c in asyn["choices"]], label
+            _deep_eq(got.likelihoods, asyn["likelihoods"], f"{label} likelihoods(async)")
 
-    async def run_ours():
-        return await async_consolidate_chat_completions(_mk_completion(list(contents)), aembed)
-
-    try:
-        want_async = asyncio.run(run_ref())
-        want_sync = ref_consolidation.consolidate_chat_completions(
-            _mk_completion(list(contents)), fake_embed, None
-        )
-    except Exception as e:
-        if "unhashable" in str(e):
-            return
-        with pytest.raises(type(e)):
-            asyncio.run(run_ours())
-        return
-    got = asyncio.run(run_ours())
-    # ours always equals the reference's SYNC behavior
-    assert len(got.choices) == len(want_sync.choices)
-    for g, w in zip(got.choices, want_sync.choices):
-        assert (g.index, g.finish_reason, g.message.content) == (w.index, w.finish_reason, w.message.content)
-    _deep_eq(got.likelihoods, want_sync.likelihoods, "likelihoods(sync)")
-    assert got.usage.model_dump() == want_sync.usage.model_dump()
-    # and equals the async result wherever the reference hasn't drifted
-    ref_agrees = all(
-        a.message.content == b.message.content
-        for a, b in zip(want_async.choices, want_sync.choices)
-    ) and want_async.likelihoods == want_sync.likelihoods
-    if ref_agrees:
-        for g, w in zip(got.choices, want_async.choices):
-            assert g.message.content == w.message.content
-        _deep_eq(got.likelihoods, want_async.likelihoods, "likelihoods(async)")
+    _replay(golden, "async_consolidation", 60,
+            lambda c: asyncio.run(async_consolidate_chat_completions(_mk_completion(c), aembed)),
+            check=check, on_crash=_same_crash_unless_unhashable)
 
 
 # ---------------------------------------------------------------------------
 # Key-based aligner differential (C42-C44, the dormant-but-shipped L1b)
 # ---------------------------------------------------------------------------
 
-@pytest.fixture(scope="module")
-def ref_key(ref):
-    for sub in ("key_selection", "fuzzy_key_selection", "key_based_alignment"):
-        name = f"_refk.{sub}"
-        if name not in sys.modules:
-            spec = importlib.util.spec_from_file_location(name, os.path.join(REF_UTILS, f"{sub}.py"))
-            mod = importlib.util.module_from_spec(spec)
-            sys.modules[name] = mod
-            spec.loader.exec_module(mod)
-    return sys.modules["_refk.key_based_alignment"]
+def _records(lists_of_records):
+    return [r for lst in lists_of_records for r in lst]
 
 
-# record-shaped candidates: lists of dicts with scalar fields (what key-based
-# alignment exists for), plus arbitrary JSON to exercise its fallbacks
-_record = st.dictionaries(
-    st.sampled_from(["id", "name", "qty", "price", "tag"]),
-    st.one_of(st.integers(min_value=0, max_value=30), ascii_text, st.none(),
-              st.floats(allow_nan=False, allow_infinity=False, width=16)),
-    min_size=1, max_size=4,
-)
-_record_lists = st.lists(st.lists(_record, max_size=4), min_size=2, max_size=4)
+def test_key_based_recursive_align_matches_reference(golden):
+    """Record-shaped candidates (lists of dicts with scalar fields — what
+    key-based alignment exists for) plus arbitrary JSON for its fallbacks."""
+    _replay(golden, "key_based_recursive_align", 100, lambda v: recursive_align(v, "levenshtein", 0.5))
 
 
-@settings(max_examples=_DEEP * 100, deadline=None, suppress_health_check=[HealthCheck.too_slow])
-@given(st.one_of(_record_lists, st.lists(json_values, min_size=2, max_size=4)))
-def test_key_based_recursive_align_matches_reference(ref_key, values):
-    from kllms_amd.consensus.key_based_alignment import recursive_align
-
-    try:
-        want, want_km = ref_key.recursive_align(list(values), "levenshtein", 0.5)
-    except Exception as e:
-        _assert_known_ref_crash(e)
-        return
-    got, got_km = recursive_align(list(values), "levenshtein", 0.5)
-    _deep_eq(list(got), list(want), "aligned")
-    _deep_eq(got_km, want_km, "key_mappings")
-
-
-@settings(max_examples=_DEEP * 100, deadline=None, suppress_health_check=[HealthCheck.too_slow])
-@given(_record_lists)
-def test_key_selection_matches_reference(ref_key, lists_of_records):
+def test_key_selection_matches_reference(golden):
     """The cascade's chosen alignment keys must match (C42/C43)."""
-    import _refk.key_selection as ref_sel  # type: ignore[import-not-found]
-
-    from kllms_amd.consensus import key_selection as our_sel
-
-    records = [r for lst in lists_of_records for r in lst]
-    try:
-        want = ref_sel.select_best_keys(list(records))
-    except Exception as e:
-        # ValueError("No extractions"/"No scalar candidate paths") must
-        # reproduce identically on our side (crash parity)
-        with pytest.raises(type(e)):
-            our_sel.select_best_keys(list(records))
-        return
-    got = our_sel.select_best_keys(list(records))
-    _deep_eq(got.model_dump(), want.model_dump(), "selected_keys")
+    _replay(golden, "key_selection", 100,
+            lambda v: key_selection.select_best_keys(_records(v)).model_dump(), on_crash=_same_crash)
 
 
-@settings(max_examples=_DEEP * 100, deadline=None, suppress_health_check=[HealthCheck.too_slow])
-@given(st.lists(json_values, min_size=1, max_size=5))
-def test_compute_similarity_scores_matches_reference(ref, values):
-    from kllms_amd.consensus.similarity import compute_similarity_scores
-
-    want = ref.compute_similarity_scores(
-        list(values), ref.ConsensusSettings(string_similarity_method="levenshtein"), fake_embed
-    )
-    got = compute_similarity_scores(
-        list(values), ConsensusSettings(string_similarity_method="levenshtein"), fake_embed
-    )
-    _deep_eq(list(got), list(want), "scores")
+def test_compute_similarity_scores_matches_reference(golden):
+    _replay(golden, "compute_similarity_scores", 100,
+            lambda v: list(compute_similarity_scores(v, _lev(), fake_embed)))
 
 
-@settings(max_examples=_DEEP * 100, deadline=None, suppress_health_check=[HealthCheck.too_slow])
-@given(st.lists(st.lists(st.integers(min_value=0, max_value=9), min_size=1, max_size=5),
-                min_size=2, max_size=4))
-def test_sort_by_original_majority_matches_reference(ref, originals):
+def test_sort_by_original_majority_matches_reference(golden):
     """Condorcet column ordering (C41): identical aligned permutations feed
     both implementations; identity-keyed original-position lookup must agree."""
-    import random
+    def ours(originals):
+        rng = random.Random(sum(len(o) for o in originals))
+        perm = list(range(min(len(o) for o in originals)))
+        rng.shuffle(perm)
+        # identity lookup requires the SAME cell objects; ints are interned for
+        # this value range, so aligned and originals share identities
+        aligned = [[row[j] for j in perm] for row in originals]
+        got = sort_by_original_majority(aligned, [list(o) for o in originals])
+        return [list(got[0]), list(got[1])]
 
-    from kllms_amd.consensus import sort_by_original_majority
-
-    ms = sys.modules["_refk.majority_sorting"]
-    rng = random.Random(sum(len(o) for o in originals))
-    width = min(len(o) for o in originals)
-    perm = list(range(width))
-    rng.shuffle(perm)
-    aligned = [[row[j] for j in perm] for row in originals]
-    # identity lookup requires the SAME cell objects; ints are interned for
-    # this value range, so both sides see consistent identities
-    want = ms.sort_by_original_majority([list(r) for r in aligned], [list(o) for o in originals])
-    got = sort_by_original_majority([list(r) for r in aligned], [list(o) for o in originals])
-    _deep_eq(list(got[0]), list(want[0]), "sorted_lists")
-    _deep_eq(list(got[1]), list(want[1]), "orig_idx")
+    _replay(golden, "sort_by_original_majority", 100, ours)
 
 
-@settings(max_examples=_DEEP * 120, deadline=None, suppress_health_check=[HealthCheck.too_slow])
-@given(json_values)
-def test_intermediary_cleanup_matches_reference(ref, value):
-    from kllms_amd.consensus.values import intermediary_consensus_cleanup
-
-    _deep_eq(
-        intermediary_consensus_cleanup(value),
-        ref.intermediary_consensus_cleanup(value),
-        "cleanup",
-    )
+def test_intermediary_cleanup_matches_reference(golden):
+    _replay(golden, "intermediary_cleanup", 120, intermediary_consensus_cleanup)
 
 
-@settings(max_examples=_DEEP * 120, deadline=None, suppress_health_check=[HealthCheck.too_slow])
-@given(st.lists(st.floats(min_value=0.0, max_value=1.0, allow_nan=False), max_size=10))
-def test_outlier_cutoff_matches_reference(ref, data):
-    from kllms_amd.consensus import low_cutoff_bound, remove_outliers
+def test_outlier_cutoff_matches_reference(golden):
+    def check(got, want, label):
+        assert got[0] == pytest.approx(want[0], abs=1e-12), label
+        _deep_eq(got[1], want[1], label)
 
-    assert low_cutoff_bound(list(data)) == pytest.approx(ref.low_cutoff_bound(list(data)), abs=1e-12)
-    _deep_eq(remove_outliers(list(data)), ref.remove_outliers(list(data)), "outliers")
+    _replay(golden, "outlier_cutoff", 120,
+            lambda d: [low_cutoff_bound(list(d)), remove_outliers(list(d))], check=check)
 
 
-@settings(max_examples=_DEEP * 200, deadline=None, suppress_health_check=[HealthCheck.too_slow])
-@given(ascii_text)
-def test_string_normalization_matches_reference(ref, s):
+def test_string_normalization_matches_reference(golden):
     """normalize_string + sanitize_value: the voting/similarity equivalence
     keys (transliteration itself is the shared stub; the lower/strip/regex
     logic is independent code on each side)."""
-    from kllms_amd.consensus.similarity import normalize_string, sanitize_value
+    def check(got, want, label):
+        assert got == want, label
 
-    assert normalize_string(s) == ref.normalize_string(s)
-    assert sanitize_value(s) == ref.sanitize_value(s)
-
-
-@settings(max_examples=_DEEP * 200, deadline=None, suppress_health_check=[HealthCheck.too_slow])
-@given(st.one_of(st.booleans(), st.integers(-10**6, 10**6),
-                 st.floats(allow_nan=False, allow_infinity=False)),
-       st.one_of(st.booleans(), st.integers(-10**6, 10**6),
-                 st.floats(allow_nan=False, allow_infinity=False)))
-def test_numerical_similarity_matches_reference(ref, a, b):
-    from kllms_amd.consensus.similarity import numerical_similarity
-
-    assert numerical_similarity(a, b) == pytest.approx(ref.numerical_similarity(a, b), abs=1e-12)
+    _replay(golden, "string_normalization", 200,
+            lambda s: [normalize_string(s), sanitize_value(s)], check=check)
 
 
-@settings(max_examples=_DEEP * 100, deadline=None, suppress_health_check=[HealthCheck.too_slow])
-@given(_record_lists)
-def test_fuzzy_key_selection_matches_reference(ref_key, lists_of_records):
+def test_numerical_similarity_matches_reference(golden):
+    _replay(golden, "numerical_similarity", 200,
+            lambda x: numerical_similarity(x[0], x[1]), check=_approx(1e-12))
+
+
+def test_fuzzy_key_selection_matches_reference(golden):
     """C43: canonicalized (fuzzy) key cascade and the fuzzy-fallback picker
     must agree with the reference, incl. the stability-tuple tie-break."""
-    import _refk.fuzzy_key_selection as ref_fuzzy  # type: ignore[import-not-found]
-
-    from kllms_amd.consensus import fuzzy_key_selection as our_fuzzy
-
-    records = [r for lst in lists_of_records for r in lst]
-    try:
-        want = ref_fuzzy.select_best_keys_with_fuzzy_fallback(list(records))
-    except Exception as e:
-        with pytest.raises(type(e)):
-            our_fuzzy.select_best_keys_with_fuzzy_fallback(list(records))
-        return
-    got = our_fuzzy.select_best_keys_with_fuzzy_fallback(list(records))
-    _deep_eq(got.model_dump(), want.model_dump(), "fuzzy_selected_keys")
+    _replay(golden, "fuzzy_key_selection", 100,
+            lambda v: fuzzy_key_selection.select_best_keys_with_fuzzy_fallback(_records(v)).model_dump(),
+            on_crash=_same_crash)
