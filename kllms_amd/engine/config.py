@@ -155,6 +155,13 @@ class EngineConfig(BaseModel):
     # constrained decoding: allow optional JSON whitespace between tokens
     # (default emits compact JSON — smaller DFA, fewer wasted tokens)
     constrained_whitespace: bool = False
+    # constrained decoding: keep each stream's DFA state and the per-state
+    # mask tables on the device, so the sampler gathers its own mask row and
+    # advances the state itself (no per-step host mask assembly + upload).
+    # Results are identical to the host path. The environment variable
+    # KLLMS_DEVICE_CONSTRAINTS=1/0, read once at engine construction,
+    # overrides this field.
+    device_constraints: bool = False
     # cross-request prefix caching: full prompt blocks are published to a
     # digest-keyed cache; later prompts sharing the prefix skip re-prefilling
     # it (LRU + eviction under allocator pressure)

@@ -843,6 +843,53 @@ def _dfa_vocab_product(trans: np.ndarray, tok_bytes: List[Optional[bytes]],
     return next_state
 
 
+class DeviceTables:
+    """One constraint's tables resident on one device (see
+    JsonSchemaConstraint.device_tables):
+
+    - mask      [S, W] int32   per-state allowed-token bitmask (EOS-on-accepting
+                               and dead-end-guard bits already folded in)
+    - trans     [S, 256] int16 byte DFA, bit pattern of the uint16 table
+                               (0xFFFF = dead; reinterpret as unsigned)
+    - tok_off   [V+1] int32    token t's bytes are tok_bytes[tok_off[t]:tok_off[t+1]]
+    - tok_bytes [sum len] uint8
+    - S, W, eos_id             scalars (eos_id = -1 when the tokenizer has none)
+    """
+
+    __slots__ = ("mask", "trans", "tok_off", "tok_bytes", "S", "W", "eos_id", "_desc")
+
+    def __init__(self, mask, trans, tok_off, tok_bytes, S: int, W: int, eos_id: int):
+        self.mask = mask
+        self.trans = trans
+        self.tok_off = tok_off
+        self.tok_bytes = tok_bytes
+        self.S = S
+        self.W = W
+        self.eos_id = eos_id
+        self._desc = [mask.data_ptr(), trans.data_ptr(), tok_off.data_ptr(),
+                      tok_bytes.data_ptr(), S, W]
+
+    def descriptor(self) -> List[int]:
+        """The sampler's per-stream descriptor row: the four table addresses,
+        then S and W."""
+        return self._desc
+
+    def advance(self, state: int, token: int) -> int:
+        """JsonSchemaConstraint.advance recomputed from these tables alone:
+        walk the token's bytes through `trans` (no next_state lookup)."""
+        if token == self.eos_id:
+            return state
+        beg, end = int(self.tok_off[token]), int(self.tok_off[token + 1])
+        if end == beg:
+            return state
+        cur = state
+        for b in self.tok_bytes[beg:end].tolist():
+            cur = int(self.trans[cur, b]) & 0xFFFF
+            if cur == 0xFFFF:
+                return state
+        return cur
+
+
 class JsonSchemaConstraint:
     """Per-request constraint handle. State is an int DFA state; tables are
     cached per (schema, tokenizer vocab)."""
@@ -865,9 +912,19 @@ class JsonSchemaConstraint:
         self.start_state = start
         self.accepting = accepting
         self.eos_id = tokenizer.eos_id
+        self.trans = trans
+        # device -> DeviceTables; the dict object is shared by every handle
+        # that adopts these cached tables
+        self._device_tables: Dict[str, DeviceTables] = {}
 
         # token byte strings
         tok_bytes: List[Optional[bytes]] = [tokenizer.token_bytes(i) for i in range(V)]
+        lens = np.fromiter((len(b) if b else 0 for b in tok_bytes), dtype=np.int64, count=V)
+        tok_off = np.zeros(V + 1, dtype=np.int64)
+        np.cumsum(lens, out=tok_off[1:])
+        assert tok_off[-1] < 2 ** 31
+        self._tok_off = tok_off.astype(np.int32)
+        self._tok_bytes = np.frombuffer(b"".join(b for b in tok_bytes if b), dtype=np.uint8)
         # next_state[S, V] via a LEVEL-VECTORIZED TRIE walk: tokens sharing a
         # byte prefix (BPE merge families, the byte tokenizer's <tkN> filler
         # block) are walked once per unique prefix instead of once per token —
@@ -922,3 +979,30 @@ class JsonSchemaConstraint:
 
     def is_final(self, state: int) -> bool:
         return bool(self._terminal[state])
+
+    def device_tables(self, device) -> DeviceTables:
+        """The tables the device-resident constraint path reads, uploaded
+        once per device and cached on the constraint.
+
+        Constraint objects are cached process-wide (_TABLE_CACHE) and never
+        evicted, and their host tables (next_state[S, V] above all) are ~16x
+        larger than these copies, so the device copies need no eviction
+        either: they live exactly as long as the constraint."""
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        key = str(dev)
+        tabs = self._device_tables.get(key)
+        if tabs is None:
+            S = int(self.trans.shape[0])
+            tabs = DeviceTables(
+                mask=self._mask_t.to(dev).contiguous(),
+                trans=torch.from_numpy(np.ascontiguousarray(self.trans).view(np.int16)).to(dev),
+                tok_off=torch.from_numpy(self._tok_off).to(dev),
+                # frombuffer arrays are read-only; copy so torch owns the bytes
+                tok_bytes=torch.from_numpy(self._tok_bytes.copy()).to(dev),
+                S=S, W=int(self._mask_t.shape[1]),
+                eos_id=-1 if self.eos_id is None else int(self.eos_id),
+            )
+            self._device_tables[key] = tabs
+        return tabs

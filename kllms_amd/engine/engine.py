@@ -13,6 +13,7 @@ summed across the n streams.
 
 from __future__ import annotations
 
+import os
 import time
 from dataclasses import dataclass, field
 from typing import Any, List, Optional, Tuple
@@ -105,6 +106,15 @@ class _DecodeBatchState:
         self.top_ks = torch.tensor([s.sampling.top_k for s in streams], dtype=torch.int32, device=dev)
         self.seeds = torch.tensor([s.seed for s in streams], dtype=torch.int64, device=dev)
         self.steps = torch.tensor([s.step for s in streams], dtype=torch.int64, device=dev)
+        # device-resident constraint path: per-stream DFA state, the [B, 6]
+        # table descriptor, and the table objects themselves (held so the
+        # addresses in the descriptor stay valid for the life of this state).
+        # Built only when some stream is constrained.
+        self.fsm_state: Optional[torch.Tensor] = None
+        self.fsm_tabs: Optional[torch.Tensor] = None
+        self.fsm_tables: Optional[list] = None
+        if engine.device_constraints and any(s.constraint is not None for s in streams):
+            self.fsm_tables, self.fsm_state, self.fsm_tabs = engine._fsm_tensors(streams)
 
     def apply_bt_updates(self, updates: List[tuple]) -> None:
         need = max(j for _, j, _ in updates) + 1
@@ -152,6 +162,12 @@ class LLMEngine:
             dev_for_ar = self.device if self.device.type == "cuda" else torch.device("cpu")
             maybe_init_custom_allreduce(self.ctx, dev_for_ar)
 
+        # device-resident constrained decoding: config field, overridden by
+        # KLLMS_DEVICE_CONSTRAINTS=1/0 (read once, here)
+        env_dc = os.environ.get("KLLMS_DEVICE_CONSTRAINTS")
+        if env_dc not in (None, "", "0", "1"):
+            raise ValueError(f"KLLMS_DEVICE_CONSTRAINTS must be 0 or 1, got {env_dc!r}")
+        self.device_constraints = config.device_constraints if not env_dc else env_dc == "1"
         # monotonic per-request counter for unseeded-request RNG derivation
         self._seed_counter = 0
         # device-tensor cache for per-request logit_bias dicts (keyed by id)
@@ -289,6 +305,41 @@ class LLMEngine:
             else:
                 mask[i] = s.constraint.allowed_mask(s.constraint_state)
         return mask.to(self.device)
+
+    def _fsm_tensors(self, streams: List[_Stream]):
+        """Device-resident constraint inputs for ops.sample_fsm: the per-stream
+        device tables (None = unconstrained), the int32 DFA states seeded from
+        the host mirror (0 for unconstrained streams) and the descriptor."""
+        dev = self.device
+        tables = [s.constraint.device_tables(dev) if s.constraint is not None else None
+                  for s in streams]
+        fsm_state = torch.tensor(
+            [s.constraint_state if s.constraint is not None else 0 for s in streams],
+            dtype=torch.int32, device=dev)
+        return tables, fsm_state, ops.fsm_descriptor(tables, dev)
+
+    def _fsm_dense_mask(self, streams: List[_Stream], tables: list) -> torch.Tensor:
+        """[B, W] mask for _topk_logprobs, gathered on the device from each
+        stream's mask table by its (pre-advance) host-mirrored state; all-ones
+        rows for unconstrained streams."""
+        W = (self.arch.vocab_size + 31) // 32
+        full = torch.full((W,), -1, dtype=torch.int32, device=self.device)
+        return torch.stack([
+            t.mask[s.constraint_state] if t is not None else full
+            for s, t in zip(streams, tables)
+        ])
+
+    def _advance_mirror(self, s: _Stream, tok: int, dev_state: Optional[int]) -> None:
+        """Advance the host mirror of a constrained stream's DFA state; on the
+        device-resident path also check the kernel's post-sample state against
+        it, so any divergence is an error and never invalid JSON."""
+        new = s.constraint.advance(s.constraint_state, tok)
+        if dev_state is not None and dev_state != new:
+            raise RuntimeError(
+                f"device constraint state diverged from the host mirror: request "
+                f"{s.req_idx} stream {s.stream_idx}, token {tok}, device state "
+                f"{dev_state}, host state {new} (from {s.constraint_state})")
+        s.constraint_state = new
 
     def _apply_penalties(self, logits: torch.Tensor, streams: List[_Stream]) -> torch.Tensor:
         """frequency/presence penalties and logit_bias (OpenAI semantics),
@@ -683,12 +734,25 @@ class LLMEngine:
     def _sample_state(self, state: "_DecodeBatchState", logits: torch.Tensor) -> bool:
         streams = state.streams
         logits = self._apply_penalties(logits, streams)
-        mask = self._constraint_mask(streams)
-        tokens, logprobs = ops.sample(
-            logits, state.temps, state.top_ps, state.top_ks, state.seeds, state.steps, mask
-        )
         K = max((s.sampling.top_logprobs for s in streams), default=0)
+        fsm = state.fsm_state is not None
+        if fsm:
+            # the mask never leaves the device: the sampler gathers its row by
+            # state and advances the state itself. top_logprobs still needs a
+            # dense mask, gathered D2D BEFORE the kernel moves the states on.
+            mask = self._fsm_dense_mask(streams, state.fsm_tables) if K > 0 else None
+            tokens, logprobs = ops.sample_fsm(
+                logits, state.temps, state.top_ps, state.top_ks, state.seeds, state.steps,
+                state.fsm_state, state.fsm_tables, state.fsm_tabs
+            )
+        else:
+            mask = self._constraint_mask(streams)
+            tokens, logprobs = ops.sample(
+                logits, state.temps, state.top_ps, state.top_ks, state.seeds, state.steps, mask
+            )
         parts = [tokens.to(torch.float64), logprobs.to(torch.float64)]
+        if fsm:
+            parts.append(state.fsm_state.to(torch.float64))
         if K > 0:
             tl_idx, tl_vals = self._topk_logprobs(logits, mask, K)
             parts += [tl_idx.reshape(-1).to(torch.float64), tl_vals.reshape(-1).to(torch.float64)]
@@ -701,8 +765,13 @@ class LLMEngine:
         B = tokens.shape[0]
         tokens_l = [int(x) for x in packed[:B].tolist()]
         logprobs_l = packed[B : 2 * B].tolist()
+        off = 2 * B
+        dev_states = None
+        if fsm:
+            dev_states = [int(x) for x in packed[off : off + B].tolist()]
+            off += B
         if K > 0:
-            flat = packed[2 * B :].tolist()
+            flat = packed[off:].tolist()
             self._append_topk(streams, K, flat[: B * K], flat[B * K :])
         any_done = False
         for i, s in enumerate(streams):
@@ -710,7 +779,7 @@ class LLMEngine:
             s.step += 1
             s.last_token = tok
             if s.constraint is not None:
-                s.constraint_state = s.constraint.advance(s.constraint_state, tok)
+                self._advance_mirror(s, tok, dev_states[i] if fsm else None)
             s.out.token_ids.append(tok)
             s.out.logprobs.append(logprobs_l[i])
             self._check_stop(s)
@@ -722,9 +791,17 @@ class LLMEngine:
         subsequent steps go through the device-resident _sample_state path."""
         logits = self._apply_penalties(logits, streams)
         temps, top_ps, top_ks, seeds, steps = self._sampling_tensors(streams)
-        mask = self._constraint_mask(streams)
-        tokens, logprobs = ops.sample(logits, temps, top_ps, top_ks, seeds, steps, mask)
         K = max((s.sampling.top_logprobs for s in streams), default=0)
+        dev_states = None
+        if self.device_constraints and any(s.constraint is not None for s in streams):
+            tables, fsm_state, tabs = self._fsm_tensors(streams)
+            mask = self._fsm_dense_mask(streams, tables) if K > 0 else None
+            tokens, logprobs = ops.sample_fsm(
+                logits, temps, top_ps, top_ks, seeds, steps, fsm_state, tables, tabs)
+            dev_states = fsm_state.tolist()
+        else:
+            mask = self._constraint_mask(streams)
+            tokens, logprobs = ops.sample(logits, temps, top_ps, top_ks, seeds, steps, mask)
         if K > 0:
             tl_idx, tl_vals = self._topk_logprobs(logits, mask, K)
             self._append_topk(streams, K, tl_idx.reshape(-1).tolist(), tl_vals.reshape(-1).tolist())
@@ -735,7 +812,7 @@ class LLMEngine:
             s.step += 1
             s.last_token = tok
             if s.constraint is not None:
-                s.constraint_state = s.constraint.advance(s.constraint_state, tok)
+                self._advance_mirror(s, tok, dev_states[i] if dev_states is not None else None)
             s.out.token_ids.append(tok)
             s.out.logprobs.append(logprobs_l[i])
             self._check_stop(s)

@@ -179,6 +179,62 @@ def sample(
     return torch_ref.sample(logits, temperatures, top_ps, top_ks, seeds, steps, mask)
 
 
+def fsm_descriptor(tables, device) -> torch.Tensor:
+    """[B, 6] int64 descriptor for sample_fsm: per stream the device addresses
+    of mask / trans / tok_off / tok_bytes, then S and W; an all-zero row for
+    an unconstrained stream (``None``)."""
+    rows = [t.descriptor() if t is not None else [0] * 6 for t in tables]
+    return torch.tensor(rows, dtype=torch.int64).reshape(len(rows), 6).to(device)
+
+
+def _fsm_eos(tables) -> int:
+    eos = {t.eos_id for t in tables if t is not None}
+    if len(eos) > 1:
+        raise ValueError(f"sample_fsm: streams disagree on eos_id: {sorted(eos)}")
+    return eos.pop() if eos else -1
+
+
+def sample_fsm(
+    logits: torch.Tensor,
+    temperatures: torch.Tensor,
+    top_ps: torch.Tensor,
+    top_ks: torch.Tensor,
+    seeds: torch.Tensor,
+    steps: torch.Tensor,
+    fsm_state: torch.Tensor,
+    tables,
+    tabs: Optional[torch.Tensor] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Constrained sampling with the DFA state on the device.
+
+    ``fsm_state`` ([B] int32) is each stream's DFA state: the kernel gathers
+    the stream's mask row from its device table by state, samples exactly as
+    ``sample`` does, and advances the state IN PLACE by the chosen token. A
+    constrained stream whose state is outside its table is sampled unmasked
+    and its state set to -1 for the caller to turn into an error.
+
+    ``tables`` is the per-stream list of constrained.DeviceTables (``None``
+    for an unconstrained stream: no mask, state untouched); the caller keeps
+    them alive until the launch has run. ``tabs`` is ``fsm_descriptor(tables)``
+    when the caller has it cached.
+    """
+    B = logits.shape[0]
+    if len(tables) != B:
+        raise ValueError(f"sample_fsm: {len(tables)} tables for {B} rows")
+    if logits.is_cuda and not _force_torch():
+        if tabs is None:
+            tabs = fsm_descriptor(tables, logits.device)
+        tokens = torch.empty(B, dtype=torch.long, device=logits.device)
+        logprobs = torch.empty(B, dtype=torch.float32, device=logits.device)
+        _hip_or_raise().sample_fsm(
+            tokens, logprobs, logits, temperatures, top_ps, top_ks, seeds, steps,
+            fsm_state, tabs, _fsm_eos(tables),
+        )
+        return tokens, logprobs
+    return torch_ref.sample_fsm(logits, temperatures, top_ps, top_ks, seeds, steps,
+                                fsm_state, tables)
+
+
 def moe_gateup(
     act: torch.Tensor,
     x: torch.Tensor,

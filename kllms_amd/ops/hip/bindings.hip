@@ -17,6 +17,7 @@ extern "C" void launch_attn_decode_partial(float*, const bf16_t*, const void*, c
 extern "C" __global__ void attn_decode_reduce_kernel(bf16_t*, const float*, const int*, int, int, int, int);
 extern "C" __global__ void attn_prefill_kernel(bf16_t*, const bf16_t*, const bf16_t*, const bf16_t*, const int*, const int*, const int*, float, int, int, int, int);  // grouped: [G], [G], [G*8]
 extern "C" __global__ void sample_kernel(int64_t*, float*, const float*, const float*, const float*, const int*, const int64_t*, const int64_t*, const uint32_t*, int, float*);
+extern "C" __global__ void sample_fsm_kernel(int64_t*, float*, const float*, const float*, const float*, const int*, const int64_t*, const int64_t*, int32_t*, const int64_t*, int, int);
 extern "C" __global__ void mfma_selftest_kernel(float*, const bf16_t*, const bf16_t*);
 
 #define CHECK_BF16_CONTIG(t) \
@@ -181,6 +182,41 @@ void sample(torch::Tensor tokens, torch::Tensor logprobs, torch::Tensor logits,
                      dbg.numel() ? dbg.data_ptr<float>() : nullptr);
 }
 
+// Constrained sampling with the DFA state on the device: `tabs` [B, 6] holds
+// per-stream device addresses of the constraint tables (the caller keeps the
+// tables alive past the launch); `fsm_state` [B] is advanced in place.
+void sample_fsm(torch::Tensor tokens, torch::Tensor logprobs, torch::Tensor logits,
+                torch::Tensor temperatures, torch::Tensor top_ps, torch::Tensor top_ks,
+                torch::Tensor seeds, torch::Tensor steps, torch::Tensor fsm_state,
+                torch::Tensor tabs, int64_t eos_id) {
+  TORCH_CHECK(logits.is_cuda() && logits.is_contiguous() && logits.scalar_type() == at::kFloat &&
+              logits.dim() == 2, "sample_fsm: logits must be contiguous fp32 [B, V] on GPU");
+  const int B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(fsm_state.is_cuda() && fsm_state.device() == logits.device() &&
+              fsm_state.is_contiguous() && fsm_state.scalar_type() == at::kInt &&
+              fsm_state.dim() == 1 && fsm_state.size(0) == B,
+              "sample_fsm: fsm_state must be contiguous int32 [B] on the logits device");
+  TORCH_CHECK(tabs.is_cuda() && tabs.device() == logits.device() &&
+              tabs.is_contiguous() && tabs.scalar_type() == at::kLong &&
+              tabs.dim() == 2 && tabs.size(0) == B && tabs.size(1) == 6,
+              "sample_fsm: tabs must be contiguous int64 [B, 6] on the logits device");
+  TORCH_CHECK(tokens.is_cuda() && tokens.is_contiguous() && tokens.scalar_type() == at::kLong &&
+              tokens.numel() == B, "sample_fsm: tokens must be contiguous int64 [B] on GPU");
+  TORCH_CHECK(logprobs.is_cuda() && logprobs.is_contiguous() && logprobs.scalar_type() == at::kFloat &&
+              logprobs.numel() == B, "sample_fsm: logprobs must be contiguous fp32 [B] on GPU");
+  TORCH_CHECK(temperatures.numel() == B && top_ps.numel() == B && top_ks.numel() == B &&
+              seeds.numel() == B && steps.numel() == B, "sample_fsm: per-row parameters must be [B]");
+  TORCH_CHECK(eos_id >= -1 && eos_id < V, "sample_fsm: eos_id out of range");
+  if (B == 0) return;
+  const size_t lds = 16 * 256 * (sizeof(float) + sizeof(unsigned int));  // per-wave histograms
+  hipLaunchKernelGGL(sample_fsm_kernel, dim3(B), dim3(1024), lds, cur_stream(),
+                     tokens.data_ptr<int64_t>(), logprobs.data_ptr<float>(),
+                     logits.data_ptr<float>(), temperatures.data_ptr<float>(),
+                     top_ps.data_ptr<float>(), top_ks.data_ptr<int>(),
+                     seeds.data_ptr<int64_t>(), steps.data_ptr<int64_t>(),
+                     fsm_state.data_ptr<int>(), tabs.data_ptr<int64_t>(), (int)eos_id, V);
+}
+
 torch::Tensor mfma_selftest(torch::Tensor A, torch::Tensor B) {
   // D[32,32] = A[32,16] x B[16,32], verifying the fragment maps the attention
   // kernel assumes for v_mfma_f32_32x32x16_bf16.
@@ -322,6 +358,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_paged", &attn_decode_paged);
   m.def("attn_prefill", &attn_prefill);
   m.def("sample", &sample);
+  m.def("sample_fsm", &sample_fsm);
   m.def("mfma_selftest", &mfma_selftest);
   m.def("one_shot_allreduce", &one_shot_allreduce);
 }

@@ -40,7 +40,11 @@ __device__ __forceinline__ float sx_of(float x, float inv_t, float smax) {
 #define SBINS 256
 #define SRANGE 20.0f       // scaled-logit window below max covered by the histogram
 
-extern "C" __global__ void __launch_bounds__(NT) sample_kernel(
+// The sampler proper, shared by both entry points. `mrow` is THIS row's
+// allowed-token bitmask (ceil(V/32) words) or nullptr for an unmasked row.
+// Thread 0 stores the token and its logprob; the return value is the chosen
+// token and is meaningful in thread 0 only.
+__device__ __forceinline__ int sample_row(
     int64_t* __restrict__ out_tokens,     // [B]
     float* __restrict__ out_logprobs,     // [B]
     const float* __restrict__ logits,     // [B, V]
@@ -49,14 +53,13 @@ extern "C" __global__ void __launch_bounds__(NT) sample_kernel(
     const int* __restrict__ top_ks,
     const int64_t* __restrict__ seeds,
     const int64_t* __restrict__ steps,
-    const uint32_t* __restrict__ mask,    // [B, ceil(V/32)] or nullptr
+    const uint32_t* __restrict__ mrow,    // [ceil(V/32)] or nullptr
     int V, float* __restrict__ dbg) {   // dbg: [B, 16] or nullptr (diagnostics)
   const int b = blockIdx.x;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = tid / WAVE;
   const float* row = logits + (int64_t)b * V;
-  const uint32_t* mrow = mask ? mask + (int64_t)b * ((V + 31) / 32) : nullptr;
   const float temp = temperatures[b];
   const float top_p = top_ps[b];
   const int top_k = top_ks[b];
@@ -120,7 +123,7 @@ extern "C" __global__ void __launch_bounds__(NT) sample_kernel(
       out_tokens[b] = argmax_tok;
       out_logprobs[b] = row[argmax_tok] - gmax - __logf(gsum_unscaled);
     }
-    return;
+    return argmax_tok;
   }
 
   // ---- pass C: admission threshold ----------------------------------------
@@ -300,9 +303,95 @@ extern "C" __global__ void __launch_bounds__(NT) sample_kernel(
     atomicMax(&sh_best, packed);
   }
   __syncthreads();
+  const int tok = (int)(sh_best & 0xffffffffu);
   if (tid == 0) {
-    const int tok = (int)(sh_best & 0xffffffffu);
     out_tokens[b] = tok;
     out_logprobs[b] = row[tok] - gmax - __logf(gsum_unscaled);
+  }
+  return tok;
+}
+
+extern "C" __global__ void __launch_bounds__(NT) sample_kernel(
+    int64_t* __restrict__ out_tokens,     // [B]
+    float* __restrict__ out_logprobs,     // [B]
+    const float* __restrict__ logits,     // [B, V]
+    const float* __restrict__ temperatures,
+    const float* __restrict__ top_ps,
+    const int* __restrict__ top_ks,
+    const int64_t* __restrict__ seeds,
+    const int64_t* __restrict__ steps,
+    const uint32_t* __restrict__ mask,    // [B, ceil(V/32)] or nullptr
+    int V, float* __restrict__ dbg) {   // dbg: [B, 16] or nullptr (diagnostics)
+  const uint32_t* mrow =
+      mask ? mask + (int64_t)blockIdx.x * ((V + 31) / 32) : nullptr;
+  sample_row(out_tokens, out_logprobs, logits, temperatures, top_ps, top_ks,
+             seeds, steps, mrow, V, dbg);
+}
+
+// Constrained-decoding entry point: the per-stream DFA state lives on the
+// device. Each row gathers its mask from the stream's [S, W] table by state,
+// samples through the shared body, then thread 0 advances the state by
+// walking the chosen token's bytes through the byte DFA (the same product the
+// host's next_state[S, V] table tabulates, without its S*V footprint).
+//
+// tabs[b] = {mask, trans, tok_off, tok_bytes (device addresses), S, W};
+// an all-zero row marks an unconstrained stream (no mask, state untouched).
+// trans is [S, 256] 16-bit with 0xFFFF = dead; tok_off is [V+1]; token t's
+// bytes are tok_bytes[tok_off[t] .. tok_off[t+1]).
+#define FSM_DEAD 0xFFFFu
+
+extern "C" __global__ void __launch_bounds__(NT) sample_fsm_kernel(
+    int64_t* __restrict__ out_tokens,     // [B]
+    float* __restrict__ out_logprobs,     // [B]
+    const float* __restrict__ logits,     // [B, V]
+    const float* __restrict__ temperatures,
+    const float* __restrict__ top_ps,
+    const int* __restrict__ top_ks,
+    const int64_t* __restrict__ seeds,
+    const int64_t* __restrict__ steps,
+    int32_t* fsm_state,                   // [B], updated in place
+    const int64_t* __restrict__ tabs,     // [B, 6]
+    int eos_id, int V) {
+  const int b = blockIdx.x;
+  // Every thread reads the state and the descriptor HERE, before the first
+  // barrier; nothing below re-reads fsm_state.
+  const int st = fsm_state[b];
+  const int64_t* d = tabs + (int64_t)b * 6;
+  const uint32_t* mask_tab = reinterpret_cast<const uint32_t*>(d[0]);
+  const uint16_t* trans = reinterpret_cast<const uint16_t*>(d[1]);
+  const int32_t* tok_off = reinterpret_cast<const int32_t*>(d[2]);
+  const uint8_t* tok_bytes = reinterpret_cast<const uint8_t*>(d[3]);
+  const int S = (int)d[4];
+  const int W = (int)d[5];
+  const bool constrained = mask_tab != nullptr;
+  // a state outside [0, S) (or a table built for another vocab width) must
+  // not index anything: the row is sampled unmasked and flagged with -1
+  const bool valid = constrained && st >= 0 && st < S && W == (V + 31) / 32;
+  const uint32_t* mrow = valid ? mask_tab + (int64_t)st * W : nullptr;
+
+  const int tok = sample_row(out_tokens, out_logprobs, logits, temperatures,
+                             top_ps, top_ks, seeds, steps, mrow, V, nullptr);
+
+  // Ordering: thread 0 gets here only after the block's last barrier — on the
+  // sampling path the __syncthreads() that publishes sh_best, on the greedy
+  // early return the two block reductions — and every thread read `st` above
+  // the first of them, so no thread can observe the advanced state.
+  if (threadIdx.x == 0 && constrained) {
+    int ns = -1;
+    if (valid) {
+      ns = st;
+      if (tok != eos_id && tok >= 0 && tok < V) {
+        const int beg = tok_off[tok];
+        const int end = tok_off[tok + 1];
+        int cur = st;
+        for (int i = beg; i < end; ++i) {
+          const unsigned nxt = trans[(int64_t)cur * 256 + tok_bytes[i]];
+          if (nxt == FSM_DEAD || (int)nxt >= S) { cur = -1; break; }
+          cur = (int)nxt;
+        }
+        if (end > beg && cur >= 0) ns = cur;
+      }
+    }
+    fsm_state[b] = ns;
   }
 }

@@ -262,3 +262,41 @@ def sample(
 
     logprobs = base_logprobs[torch.arange(B, device=logits.device), tokens]
     return tokens, logprobs
+
+
+def sample_fsm(
+    logits: torch.Tensor,
+    temperatures: torch.Tensor,
+    top_ps: torch.Tensor,
+    top_ks: torch.Tensor,
+    seeds: torch.Tensor,
+    steps: torch.Tensor,
+    fsm_state: torch.Tensor,
+    tables,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Reference for the device-resident constraint sampler.
+
+    Gathers each stream's mask row from its tables by ``fsm_state`` (all-ones
+    for an unconstrained ``None`` stream), samples through ``sample`` and
+    advances every constrained state in place by walking the chosen token's
+    bytes through the byte DFA. A constrained stream whose state is outside
+    [0, S) is sampled unmasked and its state becomes -1."""
+    B, V = logits.shape
+    W = (V + 31) // 32
+    states = fsm_state.tolist()
+    mask = None
+    if any(t is not None for t in tables):
+        mask = torch.full((B, W), -1, dtype=torch.int32, device=logits.device)
+        for i, t in enumerate(tables):
+            if t is not None and 0 <= states[i] < t.S and t.W == W:
+                mask[i] = t.mask[states[i]]
+    tokens, logprobs = sample(logits, temperatures, top_ps, top_ks, seeds, steps, mask)
+    toks = tokens.tolist()
+    for i, t in enumerate(tables):
+        if t is None:
+            continue
+        if 0 <= states[i] < t.S and t.W == W:
+            fsm_state[i] = t.advance(states[i], toks[i])
+        else:
+            fsm_state[i] = -1
+    return tokens, logprobs
