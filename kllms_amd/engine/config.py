@@ -162,6 +162,17 @@ class EngineConfig(BaseModel):
     # KLLMS_DEVICE_CONSTRAINTS=1/0, read once at engine construction,
     # overrides this field.
     device_constraints: bool = False
+    # shared-prefix (cascade) decode attention: the streams forked from one
+    # prompt read that prompt's K/V once per GROUP (an MFMA kernel over all
+    # of the group's query rows) instead of once per stream; each stream's
+    # private suffix still goes through the per-stream kernel. Off by
+    # default; with it off nothing changes. The environment variable
+    # KLLMS_SHARED_PREFIX_ATTN=1/0, read once at engine construction,
+    # overrides this field.
+    shared_prefix_attention: bool = False
+    # groups sharing fewer keys than this are not cascaded (whole 256-key
+    # chunks are shared, so 256 is also the floor)
+    shared_prefix_min_keys: int = 256
     # cross-request prefix caching: full prompt blocks are published to a
     # digest-keyed cache; later prompts sharing the prefix skip re-prefilling
     # it (LRU + eviction under allocator pressure)

@@ -24,6 +24,7 @@ from ..models.llama import ForwardBatch
 from .config import EngineConfig, ModelArchConfig
 from .kvcache import PagedKVCache, SequenceKV
 from .sampling import SamplingParams
+from .shared_prefix import build_shared_prefix_tiles
 from .tokenizer import BaseTokenizer, load_tokenizer
 from .. import ops
 
@@ -66,8 +67,11 @@ class _Stream:
     """One active decode stream (one of a request's n samples)."""
 
     def __init__(self, req_idx: int, stream_idx: int, seq: SequenceKV, sampling: SamplingParams,
-                 seed: int, constraint_state=None, constraint=None):
+                 seed: int, constraint_state=None, constraint=None, fork_id: int = -1):
         self.req_idx = req_idx
+        # streams forked from the same prompt share a fork_id (per-engine
+        # counter); -1 = not part of a fork group
+        self.fork_id = fork_id
         self.stream_idx = stream_idx
         self.seq = seq
         self.sampling = sampling
@@ -115,6 +119,24 @@ class _DecodeBatchState:
         self.fsm_tables: Optional[list] = None
         if engine.device_constraints and any(s.constraint is not None for s in streams):
             self.fsm_tables, self.fsm_state, self.fsm_tabs = engine._fsm_tensors(streams)
+        # shared-prefix cascade metadata: rebuilt with the state, i.e. whenever
+        # membership changes. A deterministic function of the streams, so
+        # every tensor-parallel rank builds the same tables.
+        self.shared = None
+        self.n_tiles = 0
+        self.rows_cascaded = 0
+        if engine.shared_prefix_attention:
+            chunk = 256
+            tiles = build_shared_prefix_tiles(
+                [s.seq.blocks for s in streams], [s.fork_id for s in streams], bs,
+                engine.arch.num_heads // engine.arch.num_kv_heads, chunk_keys=chunk,
+                min_shared_chunks=max(1, -(-engine.config.shared_prefix_min_keys // chunk)),
+                context_lens=[s.seq.num_tokens + 1 for s in streams])
+            self.n_tiles = tiles.n_tiles
+            self.rows_cascaded = tiles.rows_cascaded
+            if tiles.n_tiles:
+                self.shared = tiles.to_tensors(dev)
+            engine._shared_prefix_rows = max(engine._shared_prefix_rows, self.rows_cascaded)
 
     def apply_bt_updates(self, updates: List[tuple]) -> None:
         need = max(j for _, j, _ in updates) + 1
@@ -168,6 +190,17 @@ class LLMEngine:
         if env_dc not in (None, "", "0", "1"):
             raise ValueError(f"KLLMS_DEVICE_CONSTRAINTS must be 0 or 1, got {env_dc!r}")
         self.device_constraints = config.device_constraints if not env_dc else env_dc == "1"
+        # shared-prefix cascade decode attention: config field, overridden by
+        # KLLMS_SHARED_PREFIX_ATTN=1/0 (read once, here)
+        env_sp = os.environ.get("KLLMS_SHARED_PREFIX_ATTN")
+        if env_sp not in (None, "", "0", "1"):
+            raise ValueError(f"KLLMS_SHARED_PREFIX_ATTN must be 0 or 1, got {env_sp!r}")
+        self.shared_prefix_attention = (
+            config.shared_prefix_attention if not env_sp else env_sp == "1")
+        # per-engine fork-group counter (_Stream.fork_id) and the most rows a
+        # decode batch cascaded during the current generate() call
+        self._fork_counter = 0
+        self._shared_prefix_rows = 0
         # monotonic per-request counter for unseeded-request RNG derivation
         self._seed_counter = 0
         # device-tensor cache for per-request logit_bias dicts (keyed by id)
@@ -562,11 +595,14 @@ class LLMEngine:
             rid = self._seed_counter
             self._seed_counter += 1
             base_seed = req.sampling.seed if req.sampling.seed is not None else (self.config.seed * 1000003 + rid)
+            fork_id = self._fork_counter
+            self._fork_counter += 1
             for si in range(max(1, req.n)):
                 seq = self.kv.fork(parent_seqs[ri])
                 cstate = req.constraint.init_state() if req.constraint is not None else None
                 st = _Stream(ri, si, seq, req.sampling, seed=base_seed + 7919 * si,
-                             constraint=req.constraint, constraint_state=cstate)
+                             constraint=req.constraint, constraint_state=cstate,
+                             fork_id=fork_id)
                 st.deadline = req.deadline if self.ctx.world_size == 1 else None
                 streams.append(st)
                 new_streams.append(st)
@@ -629,6 +665,7 @@ class LLMEngine:
     ) -> List[RequestOutput]:
         dev = self.device
         t0 = time.perf_counter()
+        self._shared_prefix_rows = 0
         outputs = self.begin_requests(requests, parent_seqs, streams)
         if dev.type == "cuda":
             torch.cuda.synchronize()
@@ -664,6 +701,8 @@ class LLMEngine:
             "decode_forward_ms": t_forward * 1000,
             "decode_sample_ms": t_sample * 1000,
             "n_streams": len(streams),
+            # most rows of one decode batch served by the shared-prefix kernel
+            "shared_prefix_rows": self._shared_prefix_rows,
         }
 
         # ---- collect ---------------------------------------------------------
@@ -703,6 +742,7 @@ class LLMEngine:
             kv_caches=self.kv.layer_caches(),
             block_tables=state.bt,
             context_lens=state.ctx,
+            shared=state.shared,
         )
         if self._graph_runner is not None:
             return self._graph_runner.run(state.ids, batch)

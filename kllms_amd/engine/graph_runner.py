@@ -12,6 +12,12 @@ Batch sizes are bucketed (config.hip_graph_batch_sizes); a decode batch of
 size B runs the smallest captured bucket >= B with tail padding. Padded lanes
 replay against a scratch KV block (slot 0 writes are masked by pointing
 padded slots at a dedicated scratch block) and their outputs are discarded.
+
+With shared-prefix attention on, every bucket also owns static cascade
+metadata (skip_chunks[bs] and tile tables for bs // 2 tiles) and is captured
+with the cascade launch in it. A step's metadata is copied in and the rest
+zeroed; all-zero metadata replays as the plain per-stream path (the cascade
+blocks return at once, no chunk is skipped).
 """
 
 from __future__ import annotations
@@ -45,6 +51,19 @@ class DecodeGraphRunner:
             "block_tables": torch.full((bs, mb), self._scratch_block, dtype=torch.int32, device=dev),
             "context_lens": torch.ones(bs, dtype=torch.int32, device=dev),
         }
+        shared = None
+        if eng.shared_prefix_attention:
+            from ..ops import SharedPrefix
+
+            nt = bs // 2   # a tile has >= 2 members except a large group's last
+            shared = SharedPrefix(
+                skip_chunks=torch.zeros(bs, dtype=torch.int32, device=dev),
+                tile_rows=torch.full((nt, 64), -1, dtype=torch.int32, device=dev),
+                tile_nmembers=torch.zeros(nt, dtype=torch.int32, device=dev),
+                tile_chunks=torch.zeros(nt, dtype=torch.int32, device=dev),
+            )
+            buf["shared"] = shared
+            buf["shared_src"] = None   # metadata object the buffers hold now
         batch = ForwardBatch(
             mode="decode",
             positions=buf["positions"],
@@ -52,6 +71,7 @@ class DecodeGraphRunner:
             kv_caches=eng.kv.layer_caches(),
             block_tables=buf["block_tables"],
             context_lens=buf["context_lens"],
+            shared=shared,
         )
         # warmup on a side stream (required before capture)
         s = torch.cuda.Stream()
@@ -99,6 +119,27 @@ class DecodeGraphRunner:
                 return bs
         return None
 
+    @staticmethod
+    def _load_shared(buf: dict, src, B: int) -> None:
+        """Copy a step's cascade metadata into the bucket's static tables and
+        zero the rest (padded lanes: skip 0; unused tiles: 0 members). The
+        metadata only changes when the decode state is rebuilt, so an
+        unchanged source object is not copied again."""
+        if buf["shared_src"] is src and buf.get("shared_B") == B:
+            return
+        dst = buf["shared"]
+        dst.skip_chunks.zero_()
+        dst.tile_nmembers.zero_()
+        dst.tile_chunks.zero_()
+        if src is not None:
+            n = src.n_tiles
+            dst.skip_chunks[:B].copy_(src.skip_chunks)
+            dst.tile_rows[:n].copy_(src.tile_rows)
+            dst.tile_nmembers[:n].copy_(src.tile_nmembers)
+            dst.tile_chunks[:n].copy_(src.tile_chunks)
+        buf["shared_src"] = src
+        buf["shared_B"] = B
+
     def run(self, ids: torch.Tensor, batch: ForwardBatch) -> torch.Tensor:
         if not self._enabled:
             return self.engine.model.forward_decode(ids, batch)
@@ -120,6 +161,12 @@ class DecodeGraphRunner:
                 self._recover_generator_state()
                 return self.engine.model.forward_decode(ids, batch)
         buf = self.buffers[bs]
+        if batch.shared is not None:
+            if "shared" not in buf or batch.shared.n_tiles > buf["shared"].n_tiles:
+                # not captured with cascade tables / more tiles than they hold
+                return self.engine.model.forward_decode(ids, batch)
+        if "shared" in buf:
+            self._load_shared(buf, batch.shared, B)
         scratch_slot = self._scratch_block * self.engine.config.kv_block_size
         buf["ids"][:B].copy_(ids)
         buf["ids"][B:].fill_(0)

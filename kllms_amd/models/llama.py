@@ -38,6 +38,9 @@ class ForwardBatch:
     cu_seqlens: Optional[torch.Tensor] = None   # [n_seq+1] int32 (prefill)
     block_tables: Optional[torch.Tensor] = None  # [B, max_blocks] int32 (decode)
     context_lens: Optional[torch.Tensor] = None  # [B] int32 (decode)
+    # shared-prefix cascade metadata (ops.SharedPrefix) for the forked streams
+    # of a decode batch; None = per-stream decode attention only
+    shared: Optional["ops.SharedPrefix"] = None
 
 
 class LlamaAttention(nn.Module):
@@ -82,7 +85,7 @@ class LlamaAttention(nn.Module):
         else:
             out = ops.attn_decode_paged(
                 q, k_cache, v_cache, batch.block_tables, batch.context_lens, self.scale,
-                k_scale, v_scale,
+                k_scale, v_scale, shared=batch.shared,
             )
         return self.o_proj(out.reshape(T, -1))
 

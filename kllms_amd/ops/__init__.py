@@ -14,6 +14,7 @@ by numerics tests to produce the oracle on-device).
 from __future__ import annotations
 
 import os
+from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import torch
@@ -134,6 +135,25 @@ def attn_prefill_varlen(
     return torch_ref.attn_prefill_varlen(q, k, v, cu_seqlens, scale)
 
 
+@dataclass
+class SharedPrefix:
+    """Shared-prefix (cascade) decode-attention metadata, int32 tensors on the
+    batch's device (engine.shared_prefix.build_shared_prefix_tiles):
+    skip_chunks [B] — leading 256-key chunks of each row that the group kernel
+    computes; tile_rows [n_tiles, 64] — member batch rows of each tile;
+    tile_nmembers [n_tiles]; tile_chunks [n_tiles] — shared chunks per tile.
+    The first member's block table addresses a tile's shared K/V."""
+
+    skip_chunks: torch.Tensor
+    tile_rows: torch.Tensor
+    tile_nmembers: torch.Tensor
+    tile_chunks: torch.Tensor
+
+    @property
+    def n_tiles(self) -> int:
+        return int(self.tile_nmembers.shape[0])
+
+
 def attn_decode_paged(
     q: torch.Tensor,
     k_cache: torch.Tensor,
@@ -143,15 +163,27 @@ def attn_decode_paged(
     scale: float,
     k_scale: Optional[torch.Tensor] = None,
     v_scale: Optional[torch.Tensor] = None,
+    shared: Optional[SharedPrefix] = None,
 ) -> torch.Tensor:
+    """``shared`` (optional) turns on the shared-prefix cascade: each tile's
+    shared K/V chunks are read once for all of its rows, the per-stream
+    kernel covers the rest. ``None`` is the per-stream path alone."""
     if q.is_cuda and not _force_torch():
         out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
         none = torch.empty(0, dtype=torch.float32, device=q.device)
-        _hip_or_raise().attn_decode_paged(
-            out, q, k_cache, v_cache, block_tables, context_lens, scale,
-            k_scale if k_scale is not None else none,
-            v_scale if v_scale is not None else none)
+        ks = k_scale if k_scale is not None else none
+        vs = v_scale if v_scale is not None else none
+        if shared is None:
+            _hip_or_raise().attn_decode_paged(
+                out, q, k_cache, v_cache, block_tables, context_lens, scale, ks, vs)
+        else:
+            _hip_or_raise().attn_decode_paged_shared(
+                out, q, k_cache, v_cache, block_tables, context_lens, scale, ks, vs,
+                shared.skip_chunks, shared.tile_rows, shared.tile_nmembers, shared.tile_chunks)
         return out
+    if shared is not None:
+        return torch_ref.attn_decode_paged_shared(
+            q, k_cache, v_cache, block_tables, context_lens, scale, k_scale, v_scale, shared)
     return torch_ref.attn_decode_paged(q, k_cache, v_cache, block_tables, context_lens, scale,
                                        k_scale, v_scale)
 

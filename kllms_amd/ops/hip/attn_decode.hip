@@ -42,11 +42,14 @@ __global__ __launch_bounds__(NTHREADS) void attn_decode_partial_t(
     const float* __restrict__ v_scale,
     const int* __restrict__ block_tables,  // [B, max_blocks]
     const int* __restrict__ context_lens,  // [B]
+    const int* __restrict__ skip_chunks,   // [B] or null: leading chunks owned by
+                                           // the shared-prefix kernel
     float scale, int num_kv_heads,
     int block_size, int max_blocks, int max_chunks, int q_tstride, int chunk_keys) {
   const int b = blockIdx.x;
   const int g_kv = blockIdx.y;
   const int chunk = blockIdx.z;
+  if (skip_chunks != nullptr && chunk < skip_chunks[b]) return;
   const int L = context_lens[b];
   const int c0 = chunk * chunk_keys;
   if (c0 >= L && chunk > 0) return;     // no keys for this chunk
@@ -258,7 +261,7 @@ __global__ __launch_bounds__(NTHREADS) void attn_decode_partial_t(
 extern "C" void launch_attn_decode_partial(
     float* partials, const bf16_t* q, const void* k_cache, const void* v_cache,
     const float* k_scale, const float* v_scale,
-    const int* block_tables, const int* context_lens, float scale,
+    const int* block_tables, const int* context_lens, const int* skip_chunks, float scale,
     int num_q_heads, int num_kv_heads, int block_size, int max_blocks,
     int max_chunks, int q_tstride, int chunk_keys, int B, int cache_fp8,
     hipStream_t stream) {
@@ -270,7 +273,8 @@ extern "C" void launch_attn_decode_partial(
   hipLaunchKernelGGL((attn_decode_partial_t<G, F>), grid, dim3(NTHREADS), lds, stream, \
                      partials, q, (const char*)k_cache, (const char*)v_cache,          \
                      k_scale, v_scale,                                                 \
-                     block_tables, context_lens, scale, num_kv_heads, block_size,      \
+                     block_tables, context_lens, skip_chunks, scale, num_kv_heads,     \
+                     block_size,                                                       \
                      max_blocks, max_chunks, q_tstride, chunk_keys)
 #define DISPATCH(G) do { if (cache_fp8) LAUNCH(G, true); else LAUNCH(G, false); } while (0)
   switch (gqa) {

@@ -13,7 +13,8 @@ extern "C" __global__ void silu_mul_kernel(bf16_t*, const bf16_t*, const bf16_t*
 extern "C" __global__ void rope_kernel(bf16_t*, bf16_t*, const int64_t*, const float*, int, int, int, int, int);
 extern "C" __global__ void store_kv_kernel(const bf16_t*, const bf16_t*, bf16_t*, bf16_t*, const int64_t*, int, int, int, int, int);
 extern "C" __global__ void store_kv_fp8_kernel(const bf16_t*, const bf16_t*, unsigned char*, unsigned char*, float*, float*, const int64_t*, int, int, int, int, int);
-extern "C" void launch_attn_decode_partial(float*, const bf16_t*, const void*, const void*, const float*, const float*, const int*, const int*, float, int, int, int, int, int, int, int, int, int, hipStream_t);
+extern "C" void launch_attn_decode_partial(float*, const bf16_t*, const void*, const void*, const float*, const float*, const int*, const int*, const int*, float, int, int, int, int, int, int, int, int, int, hipStream_t);
+extern "C" void launch_attn_decode_shared(float*, const bf16_t*, const void*, const void*, const float*, const float*, const int*, const int*, const int*, const int*, float, int, int, int, int, int, int, int, int, int, int, hipStream_t);
 extern "C" __global__ void attn_decode_reduce_kernel(bf16_t*, const float*, const int*, int, int, int, int);
 extern "C" __global__ void attn_prefill_kernel(bf16_t*, const bf16_t*, const bf16_t*, const bf16_t*, const int*, const int*, const int*, float, int, int, int, int);  // grouped: [G], [G], [G*8]
 extern "C" __global__ void sample_kernel(int64_t*, float*, const float*, const float*, const float*, const int*, const int64_t*, const int64_t*, const uint32_t*, int, float*);
@@ -110,10 +111,17 @@ void store_kv(torch::Tensor k, torch::Tensor v, torch::Tensor k_cache, torch::Te
   }
 }
 
-void attn_decode_paged(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
-                       torch::Tensor v_cache, torch::Tensor block_tables,
-                       torch::Tensor context_lens, double scale,
-                       torch::Tensor k_scale, torch::Tensor v_scale) {
+// Shared body of the two decode-attention bindings. With `shared` false this
+// is exactly the per-stream split-K path; with it true the shared-prefix
+// kernel first writes the partials of each group's leading chunks and the
+// per-stream kernel skips them (skip_chunks). The reduce is the same.
+static void attn_decode_paged_impl(torch::Tensor& out, torch::Tensor& q, torch::Tensor& k_cache,
+                                   torch::Tensor& v_cache, torch::Tensor& block_tables,
+                                   torch::Tensor& context_lens, double scale,
+                                   torch::Tensor& k_scale, torch::Tensor& v_scale, bool shared,
+                                   const int* skip_chunks, const int* tile_rows,
+                                   const int* tile_nmembers, const int* tile_chunks,
+                                   int n_tiles) {
   CHECK_BF16_CONTIG(out); CHECK_BF16_ROWS(q); CHECK_KV_CACHE(k_cache); CHECK_KV_CACHE(v_cache);
   const int B = q.size(0), H = q.size(1), D = q.size(2);
   const int KVH = k_cache.size(1), BS = k_cache.size(2);
@@ -137,16 +145,59 @@ void attn_decode_paged(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache
                     k_scale.scalar_type() == at::kFloat && v_scale.numel() == k_scale.numel(),
                 "fp8 attn_decode requires [NB, KVH, BS] fp32 k_scale/v_scale");
   }
+  if (shared && n_tiles > 0) {
+    launch_attn_decode_shared(
+        partials.data_ptr<float>(), cbf(q), k_cache.data_ptr(), v_cache.data_ptr(),
+        cache_fp8 ? k_scale.data_ptr<float>() : nullptr,
+        cache_fp8 ? v_scale.data_ptr<float>() : nullptr,
+        block_tables.data_ptr<int>(), tile_rows, tile_nmembers, tile_chunks,
+        (float)scale, B, H, KVH, (int)k_cache.size(0), BS, max_blocks, max_chunks,
+        (int)q.stride(0), n_tiles, cache_fp8, cur_stream());
+  }
   launch_attn_decode_partial(
       partials.data_ptr<float>(), cbf(q), k_cache.data_ptr(), v_cache.data_ptr(),
       cache_fp8 ? k_scale.data_ptr<float>() : nullptr,
       cache_fp8 ? v_scale.data_ptr<float>() : nullptr,
       block_tables.data_ptr<int>(), context_lens.data_ptr<int>(),
+      (shared && n_tiles > 0) ? skip_chunks : nullptr,
       (float)scale, H, KVH, BS, max_blocks, max_chunks, (int)q.stride(0), CHUNK_KEYS, B,
       cache_fp8, cur_stream());
   hipLaunchKernelGGL(attn_decode_reduce_kernel, dim3(B, H), dim3(64), 0, cur_stream(),
                      bf(out), partials.data_ptr<float>(), context_lens.data_ptr<int>(),
                      H, KVH, max_chunks, CHUNK_KEYS);
+}
+
+void attn_decode_paged(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
+                       torch::Tensor v_cache, torch::Tensor block_tables,
+                       torch::Tensor context_lens, double scale,
+                       torch::Tensor k_scale, torch::Tensor v_scale) {
+  attn_decode_paged_impl(out, q, k_cache, v_cache, block_tables, context_lens, scale,
+                         k_scale, v_scale, false, nullptr, nullptr, nullptr, nullptr, 0);
+}
+
+// Shared-prefix cascade: skip_chunks [B], tile_rows [n_tiles, 64],
+// tile_nmembers [n_tiles], tile_chunks [n_tiles], all int32 on the GPU
+// (engine.shared_prefix.build_shared_prefix_tiles). Zero tiles is the plain
+// per-stream path.
+void attn_decode_paged_shared(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
+                              torch::Tensor v_cache, torch::Tensor block_tables,
+                              torch::Tensor context_lens, double scale,
+                              torch::Tensor k_scale, torch::Tensor v_scale,
+                              torch::Tensor skip_chunks, torch::Tensor tile_rows,
+                              torch::Tensor tile_nmembers, torch::Tensor tile_chunks) {
+  const int n_tiles = tile_nmembers.numel();
+  auto ok = [](const torch::Tensor& t) {
+    return t.is_cuda() && t.is_contiguous() && t.scalar_type() == at::kInt;
+  };
+  TORCH_CHECK(ok(skip_chunks) && ok(tile_rows) && ok(tile_nmembers) && ok(tile_chunks),
+              "attn_decode_paged_shared: metadata must be contiguous int32 on GPU");
+  TORCH_CHECK(skip_chunks.numel() == q.size(0), "skip_chunks must be [B]");
+  TORCH_CHECK(tile_rows.numel() == (int64_t)n_tiles * 64, "tile_rows must be [n_tiles, 64]");
+  TORCH_CHECK(tile_chunks.numel() == n_tiles, "tile_chunks must be [n_tiles]");
+  attn_decode_paged_impl(out, q, k_cache, v_cache, block_tables, context_lens, scale,
+                         k_scale, v_scale, true, skip_chunks.data_ptr<int>(),
+                         tile_rows.data_ptr<int>(), tile_nmembers.data_ptr<int>(),
+                         tile_chunks.data_ptr<int>(), n_tiles);
 }
 
 void attn_prefill(torch::Tensor out, torch::Tensor q, torch::Tensor k, torch::Tensor v,
@@ -356,6 +407,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_inplace", &rope_inplace);
   m.def("store_kv", &store_kv);
   m.def("attn_decode_paged", &attn_decode_paged);
+  m.def("attn_decode_paged_shared", &attn_decode_paged_shared);
   m.def("attn_prefill", &attn_prefill);
   m.def("sample", &sample);
   m.def("sample_fsm", &sample_fsm);

@@ -195,6 +195,87 @@ def attn_decode_paged(
     return out
 
 
+def _paged_partial(qb, k_cache, v_cache, blocks_row, k0, k1, scale, k_scale, v_scale):
+    """Unnormalised softmax partial of one row's heads over keys [k0, k1) read
+    through ``blocks_row``: (m [H], l [H], o [H, D]) in fp32."""
+    H, D = qb.shape
+    _, KVH, BS, _ = k_cache.shape
+    rep = H // KVH
+    j0, j1 = k0 // BS, (k1 + BS - 1) // BS
+    blocks = blocks_row[j0:j1].long()
+    lo, hi = k0 - j0 * BS, k1 - j0 * BS
+    n = j1 - j0
+    kk = k_cache[blocks].permute(1, 0, 2, 3).reshape(KVH, n * BS, D)[:, lo:hi].float()
+    vv = v_cache[blocks].permute(1, 0, 2, 3).reshape(KVH, n * BS, D)[:, lo:hi].float()
+    if k_scale is not None:
+        kk = kk * k_scale[blocks].permute(1, 0, 2).reshape(KVH, n * BS)[:, lo:hi, None]
+        vv = vv * v_scale[blocks].permute(1, 0, 2).reshape(KVH, n * BS)[:, lo:hi, None]
+    kk = kk.repeat_interleave(rep, dim=0)  # [H, n, D]
+    vv = vv.repeat_interleave(rep, dim=0)
+    s = torch.einsum("hd,hnd->hn", qb, kk) * scale
+    m = s.max(dim=-1).values
+    p = torch.exp(s - m[:, None])
+    return m, p.sum(dim=-1), torch.einsum("hn,hnd->hd", p, vv)
+
+
+def attn_decode_paged_shared(
+    q: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    block_tables: torch.Tensor,
+    context_lens: torch.Tensor,
+    scale: float,
+    k_scale=None,
+    v_scale=None,
+    shared=None,
+    chunk_keys: int = 256,
+) -> torch.Tensor:
+    """Shared-prefix cascade reference, driven by the SAME metadata as the
+    HIP path (``shared``: ops.SharedPrefix), so wrong metadata gives wrong
+    numbers here too:
+
+    - every tile's chunks ``< tile_chunks[t]`` are computed for each member
+      row from the tile's FIRST member's block table only;
+    - every row's keys from ``skip_chunks[b] * chunk_keys`` on come from its
+      own block table;
+    - the partials of a row are merged by log-sum-exp in fp32.
+    """
+    if shared is None:
+        return attn_decode_paged(q, k_cache, v_cache, block_tables, context_lens, scale,
+                                 k_scale, v_scale)
+    B, H, D = q.shape
+    skip = shared.skip_chunks.tolist()
+    rows_t = shared.tile_rows.tolist()
+    nmem_t = shared.tile_nmembers.tolist()
+    chunks_t = shared.tile_chunks.tolist()
+    parts = [[] for _ in range(B)]
+    for rows, nmem, S in zip(rows_t, nmem_t, chunks_t):
+        if nmem <= 0 or S <= 0:
+            continue
+        first = block_tables[rows[0]]
+        for b in rows[:nmem]:
+            if 0 <= b < B:
+                parts[b].append(_paged_partial(q[b].float(), k_cache, v_cache, first,
+                                               0, S * chunk_keys, scale, k_scale, v_scale))
+    out = torch.empty_like(q)
+    for b in range(B):
+        L = int(context_lens[b])
+        k0 = skip[b] * chunk_keys
+        if k0 < L:
+            parts[b].append(_paged_partial(q[b].float(), k_cache, v_cache, block_tables[b],
+                                           k0, L, scale, k_scale, v_scale))
+        if not parts[b]:
+            out[b] = 0
+            continue
+        m = torch.stack([p[0] for p in parts[b]])          # [P, H]
+        M = m.max(dim=0).values
+        w = torch.exp(m - M)                                # [P, H]
+        l = (torch.stack([p[1] for p in parts[b]]) * w).sum(dim=0)
+        o = (torch.stack([p[2] for p in parts[b]]) * w[:, :, None]).sum(dim=0)
+        out[b] = (o / l[:, None]).to(q.dtype)
+    return out
+
+
 # --- sampling -----------------------------------------------------------------
 
 def _stream_generator(seed: int, step: int, device) -> torch.Generator:

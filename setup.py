@@ -21,6 +21,7 @@ SOURCES = [
         "bindings.hip",
         "elementwise.hip",
         "attn_decode.hip",
+        "attn_decode_shared.hip",
         "attn_prefill.hip",
         "sampling.hip",
         "mfma_selftest.hip",
