@@ -124,6 +124,16 @@ class EngineConfig(BaseModel):
     weights_path: Optional[str] = None  # safetensors dir; None = random init
     dtype: Literal["bfloat16", "float32", "float16"] = "bfloat16"
     seed: int = 0
+    # "bf16" (default: weights in the compute dtype) or "fp8_e4m3": the qkv,
+    # o, gate_up and down projections of every layer are quantised at load to
+    # OCP e4m3 with one fp32 scale per output channel (half the weight bytes
+    # streamed per decode step and held in HBM; the freed HBM goes to the KV
+    # pool) and run through the weight-only fp8 x bf16 HIP GEMM. embed_tokens
+    # and lm_head stay bf16. Below the bf16 numerics, hence opt-in; llama-
+    # family models only, and on the GPU only with dtype="bfloat16". The
+    # environment variable KLLMS_WEIGHT_DTYPE=bf16/fp8_e4m3, read once at
+    # engine construction, overrides this field.
+    weight_dtype: Literal["bf16", "fp8_e4m3"] = "bf16"
 
     # Parallelism: TP over RCCL/xGMI (one process per GPU)
     tp_size: int = 1

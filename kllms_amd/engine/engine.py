@@ -197,6 +197,21 @@ class LLMEngine:
             raise ValueError(f"KLLMS_SHARED_PREFIX_ATTN must be 0 or 1, got {env_sp!r}")
         self.shared_prefix_attention = (
             config.shared_prefix_attention if not env_sp else env_sp == "1")
+        # fp8 (e4m3) layer weights: config field, overridden by
+        # KLLMS_WEIGHT_DTYPE=bf16/fp8_e4m3 (read once, here)
+        env_wd = os.environ.get("KLLMS_WEIGHT_DTYPE")
+        if env_wd not in (None, "", "bf16", "fp8_e4m3"):
+            raise ValueError(f"KLLMS_WEIGHT_DTYPE must be bf16 or fp8_e4m3, got {env_wd!r}")
+        self.weight_dtype = env_wd or config.weight_dtype
+        if self.weight_dtype == "fp8_e4m3":
+            if self.arch.arch == "mixtral":
+                raise ValueError(
+                    "weight_dtype='fp8_e4m3' does not cover Mixtral: the expert weights "
+                    "would stay bf16, and a half-quantised model would misstate the saving")
+            if self.device.type == "cuda" and config.dtype != "bfloat16":
+                raise ValueError(
+                    "weight_dtype='fp8_e4m3' on the GPU needs dtype='bfloat16' (the fp8 "
+                    f"GEMM takes bf16 activations), got dtype={config.dtype!r}")
         # per-engine fork-group counter (_Stream.fork_id) and the most rows a
         # decode batch cascaded during the current generate() call
         self._fork_counter = 0
@@ -282,8 +297,32 @@ class LLMEngine:
         else:
             model.to_device(self.device)
             model.random_init_(self.config.seed)
+        if self.weight_dtype == "fp8_e4m3":
+            self._quantize_fp8_weights(model)
         model.eval()
         return model
+
+    def _quantize_fp8_weights(self, model) -> None:
+        """Quantise every layer's qkv, o, gate_up and down projection to e4m3
+        with per-channel scales, layer by layer (each bf16 tensor is freed as
+        it goes), and hand all of them ONE bf16 scratch sized for the largest
+        projection: the large-M (packed prefill) path dequantises into it per
+        call, so no bf16 copy of the model is ever kept. embed_tokens and
+        lm_head stay as they are (logit fidelity, tied embeddings)."""
+        projs = []
+        for layer in model.layers:
+            for mod in (layer.self_attn.qkv_proj, layer.self_attn.o_proj,
+                        layer.mlp.gate_up_proj, layer.mlp.down_proj):
+                mod.quantize_fp8_()
+                projs.append(mod)
+        if self.device.type == "cuda":
+            scratch = torch.empty(max(m.weight_q.numel() for m in projs),
+                                  dtype=torch.bfloat16, device=self.device)
+            for m in projs:
+                m.fp8_scratch = scratch
+            # return the freed bf16 weights to the driver: _build_kv_cache
+            # sizes the KV pool from the HBM that is free
+            torch.cuda.empty_cache()
 
     def _build_kv_cache(self) -> PagedKVCache:
         a = self.arch

@@ -82,6 +82,55 @@ def silu_mul(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
     return torch_ref.silu_mul(gate, up)
 
 
+quantize_fp8_rows = torch_ref.quantize_fp8_rows
+
+# the shapes the HIP weight-only fp8 GEMM takes (linear_fp8w.hip)
+FP8W_MAX_M = 256
+
+
+def _fp8w_kernel_takes(x: torch.Tensor, N: int, K: int) -> bool:
+    return (x.dtype == torch.bfloat16 and 1 <= x.shape[0] <= FP8W_MAX_M
+            and K % 64 == 0 and N % 16 == 0
+            and x.stride(1) == 1 and x.stride(0) >= K and x.stride(0) % 8 == 0
+            and x.data_ptr() % 16 == 0)
+
+
+def linear_fp8w(
+    x: torch.Tensor,
+    q: torch.Tensor,
+    scale: torch.Tensor,
+    bias: Optional[torch.Tensor] = None,
+    scratch: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """``(x @ q^T) * scale + bias`` with weight-only fp8: ``q`` e4m3 [N, K],
+    ``scale`` fp32 [N] (``quantize_fp8_rows``), ``x`` [..., K].
+
+    On the GPU, bf16 ``x`` with 1 <= M <= 256, K % 64 == 0 and N % 16 == 0 runs
+    the HIP kernel (exact e4m3 x bf16 products, fp32 accumulation, scale and
+    bias on the fp32 sum). Anything else -- packed prefill above 256 rows, or
+    a shape the kernel does not take -- dequantises the weight with a second
+    HIP kernel into ``scratch`` (a reusable bf16 buffer of at least N*K
+    elements; allocated per call when None) and runs the library GEMM on it.
+    """
+    if x.is_cuda and not _force_torch():
+        C = _hip_or_raise()
+        N, K = q.shape
+        x2 = x if x.dim() == 2 else x.reshape(-1, K)
+        if x2.dtype != torch.bfloat16:
+            raise ValueError(f"linear_fp8w on GPU needs bf16 activations, got {x2.dtype}")
+        none = torch.empty(0, dtype=torch.bfloat16, device=x.device)
+        if _fp8w_kernel_takes(x2, N, K):
+            out = torch.empty((x2.shape[0], N), dtype=torch.bfloat16, device=x.device)
+            C.linear_fp8w(out, x2, q, scale, bias if bias is not None else none)
+        else:
+            if scratch is None or scratch.numel() < N * K:
+                scratch = torch.empty(N * K, dtype=torch.bfloat16, device=x.device)
+            C.dequant_fp8w(scratch, q, scale)
+            out = torch.nn.functional.linear(x2, scratch[: N * K].view(N, K), bias)
+        return out if x.dim() == 2 else out.view(*x.shape[:-1], N)
+    return torch_ref.linear_fp8w(x, q, scale, bias)
+
+
 def store_kv(
     k: torch.Tensor,
     v: torch.Tensor,

@@ -393,7 +393,82 @@ void ipc_allreduce_destroy(int64_t ctx) {
   ipc_ar_destroy(reinterpret_cast<void*>(ctx));
 }
 
+// --- weight-only fp8 GEMM (linear_fp8w.hip) ------------------------------------
+extern "C" void linear_fp8w_plan(int M, int N, int K, int n_cus, int* mt, int* splitk);
+extern "C" void launch_linear_fp8w(void* out, float* slabs, const void* x, const void* q,
+                                   const float* scale, const void* bias, int M, int N, int K,
+                                   long x_stride, int mt, int splitk, hipStream_t stream);
+extern "C" void launch_dequant_fp8w(void* w, const void* q, const float* scale, long numel,
+                                    int K, hipStream_t stream);
+
+#define CHECK_FP8W(q, scale)                                                             \
+  TORCH_CHECK((q).is_cuda() && (q).is_contiguous() && (q).dim() == 2 &&                  \
+              (q).scalar_type() == at::kFloat8_e4m3fn, "q must be contiguous e4m3 [N, K] on GPU"); \
+  TORCH_CHECK((scale).is_cuda() && (scale).is_contiguous() &&                            \
+              (scale).scalar_type() == at::kFloat && (scale).numel() == (q).size(0),     \
+              "scale must be contiguous fp32 [N] on GPU")
+
+// out[M, N] = bf16((x @ q^T) * scale + bias); bias: bf16 [N] or an empty tensor.
+// Takes 1 <= M <= 256, K % 64 == 0, N % 16 == 0, x with unit inner stride and
+// a 16-byte-aligned row stride >= K (ops.linear_fp8w routes everything else
+// through dequant_fp8w).
+void linear_fp8w(torch::Tensor out, torch::Tensor x, torch::Tensor q, torch::Tensor scale,
+                 torch::Tensor bias) {
+  CHECK_FP8W(q, scale);
+  const int64_t M = x.size(0), K = x.size(1), N = q.size(0);
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2 &&
+              x.stride(1) == 1 && x.stride(0) >= K && x.stride(0) % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "linear_fp8w: x must be a bf16 [M, K] row view with 16-byte-aligned rows");
+  TORCH_CHECK(q.size(1) == K, "linear_fp8w: x and q disagree on K");
+  TORCH_CHECK(M >= 1 && M <= 256 && K % 64 == 0 && N % 16 == 0,
+              "linear_fp8w: needs 1 <= M <= 256, K % 64 == 0, N % 16 == 0; got M=", M,
+              " N=", N, " K=", K);
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kBFloat16 && out.is_contiguous() &&
+              out.dim() == 2 && out.size(0) == M && out.size(1) == N,
+              "linear_fp8w: out must be contiguous bf16 [M, N]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(scale.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(out.data_ptr()) % 8 == 0,
+              "linear_fp8w: q/scale must be 16-byte aligned, out 8-byte aligned");
+  const void* bptr = nullptr;
+  if (bias.numel() > 0) {
+    TORCH_CHECK(bias.is_cuda() && bias.is_contiguous() && bias.scalar_type() == at::kBFloat16 &&
+                bias.numel() == N && reinterpret_cast<uintptr_t>(bias.data_ptr()) % 8 == 0,
+                "linear_fp8w: bias must be contiguous bf16 [N]");
+    bptr = bias.data_ptr();
+  }
+  const int n_cus = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  int mt = 1, splitk = 1;
+  linear_fp8w_plan((int)M, (int)N, (int)K, n_cus, &mt, &splitk);
+  float* slabs = nullptr;
+  torch::Tensor ws;
+  if (splitk > 1) {
+    ws = torch::empty({(int64_t)splitk * M * N}, torch::dtype(torch::kFloat).device(x.device()));
+    slabs = ws.data_ptr<float>();
+  }
+  launch_linear_fp8w(out.data_ptr(), slabs, x.data_ptr(), q.data_ptr(), scale.data_ptr<float>(),
+                     bptr, (int)M, (int)N, (int)K, (long)x.stride(0), mt, splitk, cur_stream());
+}
+
+// w[N, K] = bf16(fp32(q) * scale[n]) into the first N*K elements of `w` (a
+// reusable bf16 scratch); K % 16 == 0.
+void dequant_fp8w(torch::Tensor w, torch::Tensor q, torch::Tensor scale) {
+  CHECK_FP8W(q, scale);
+  CHECK_BF16_CONTIG(w);
+  TORCH_CHECK(w.numel() >= q.numel(), "dequant_fp8w: scratch smaller than the weight");
+  TORCH_CHECK(q.size(1) % 16 == 0, "dequant_fp8w: K must be a multiple of 16");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              "dequant_fp8w: q and w must be 16-byte aligned");
+  if (q.numel() == 0) return;
+  launch_dequant_fp8w(w.data_ptr(), q.data_ptr(), scale.data_ptr<float>(), (long)q.numel(),
+                      (int)q.size(1), cur_stream());
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("linear_fp8w", &linear_fp8w);
+  m.def("dequant_fp8w", &dequant_fp8w);
   m.def("levenshtein_pairs", &levenshtein_pairs);
   m.def("moe_gateup", &moe_gateup);
   m.def("moe_down", &moe_down);

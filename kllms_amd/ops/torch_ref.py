@@ -92,6 +92,42 @@ def silu_mul(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
     return (torch.nn.functional.silu(gate.float()) * up.float()).to(gate.dtype)
 
 
+# --- fp8 (e4m3) weights -------------------------------------------------------
+
+FP8_E4M3_MAX = 448.0
+
+
+def quantize_fp8_rows(w: torch.Tensor, amax: Optional[torch.Tensor] = None
+                      ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-output-channel e4m3 quantisation of a weight ``w`` [N, K]: returns
+    ``(q, scale)`` with ``q`` float8_e4m3fn [N, K] (K-contiguous) and ``scale``
+    fp32 [N], ``scale[n] = amax(|w[n, :]|) / 448`` (1.0 for an all-zero row) and
+    ``q = RNE(w / scale)`` clamped to +-448, so the NaN encodings never appear.
+    ``amax`` ([N] fp32) overrides the row maxima: a row-parallel shard passes
+    the maximum over ALL ranks' columns so that the quantised model does not
+    depend on the TP degree. The one definition for CPU and GPU (runs once at
+    load)."""
+    wf = w.float()
+    if amax is None:
+        amax = wf.abs().amax(dim=1)
+    amax = amax.float()
+    scale = torch.where(amax > 0, amax / FP8_E4M3_MAX, torch.ones_like(amax))
+    q = (wf / scale.unsqueeze(1)).clamp_(-FP8_E4M3_MAX, FP8_E4M3_MAX).to(torch.float8_e4m3fn)
+    return q.contiguous(), scale.contiguous()
+
+
+def linear_fp8w(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor,
+                bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``(x @ q^T) * scale + bias`` for e4m3 ``q`` [N, K] with per-channel fp32
+    ``scale`` [N]; any float dtype of ``x`` (fp32 accumulation, fp64 for fp64
+    input). The scale multiplies the accumulated sum, never the weights."""
+    acc = torch.float64 if x.dtype == torch.float64 else torch.float32
+    y = (x.to(acc) @ q.to(acc).t()) * scale.to(acc)
+    if bias is not None:
+        y = y + bias.to(acc)
+    return y.to(x.dtype)
+
+
 # --- paged KV cache -----------------------------------------------------------
 
 def store_kv(

@@ -23,6 +23,19 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from .. import ops
+
+
+def _quantize_fp8_(mod: nn.Module, amax: Optional[torch.Tensor] = None) -> None:
+    """Replace ``mod.weight`` (bf16) by the buffers ``weight_q`` (e4m3) and
+    ``weight_scale`` (fp32 per output channel) and free the bf16 tensor."""
+    if mod.weight is None:
+        return  # already quantised
+    q, scale = ops.quantize_fp8_rows(mod.weight.data, amax)
+    mod.weight = None  # drops the Parameter; the bf16 storage is freed here
+    mod.register_buffer("weight_q", q, persistent=False)
+    mod.register_buffer("weight_scale", scale, persistent=False)
+
 
 @dataclass
 class ParallelContext:
@@ -88,6 +101,8 @@ class ColumnParallelLinear(nn.Module):
             )
         else:
             self.register_parameter("bias", None)
+        # engine-wide dequant scratch for the fp8 large-M path (set by the engine)
+        self.fp8_scratch: Optional[torch.Tensor] = None
 
     def shard_full_tensor(self, full: torch.Tensor) -> torch.Tensor:
         """Slice this rank's shard out of the FULL fused weight (dim 0)."""
@@ -102,7 +117,15 @@ class ColumnParallelLinear(nn.Module):
             off += part
         return torch.cat(pieces, dim=0)
 
+    def quantize_fp8_(self) -> None:
+        """Opt-in fp8 (e4m3) weights: output channels are whole on every rank,
+        so the per-channel scale needs no communication."""
+        _quantize_fp8_(self)
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.weight is None:
+            return ops.linear_fp8w(x, self.weight_q, self.weight_scale, self.bias,
+                                   scratch=self.fp8_scratch)
         return torch.nn.functional.linear(x, self.weight, self.bias)
 
 
@@ -119,9 +142,26 @@ class RowParallelLinear(nn.Module):
         self.weight = nn.Parameter(
             torch.empty(out_features, self.in_features_per_rank, dtype=dtype), requires_grad=False
         )
+        # engine-wide dequant scratch for the fp8 large-M path (set by the engine)
+        self.fp8_scratch: Optional[torch.Tensor] = None
+
+    def quantize_fp8_(self) -> None:
+        """Opt-in fp8 (e4m3) weights. An output channel's columns are split
+        over the ranks, so its amax is all-reduced (MAX) first: every rank
+        then holds the matching slice of the TP=1 quantisation."""
+        if self.weight is None:
+            return
+        amax = self.weight.data.float().abs().amax(dim=1)
+        if self.ctx.world_size > 1:
+            dist.all_reduce(amax, op=dist.ReduceOp.MAX, group=self.ctx.group)
+        _quantize_fp8_(self, amax)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        y = torch.nn.functional.linear(x, self.weight)
+        if self.weight is None:
+            y = ops.linear_fp8w(x, self.weight_q, self.weight_scale,
+                                scratch=self.fp8_scratch)
+        else:
+            y = torch.nn.functional.linear(x, self.weight)
         return self.ctx.all_reduce(y)
 
 

@@ -28,6 +28,7 @@ SOURCES = [
         "allreduce.hip",
         "moe.hip",
         "levenshtein.hip",
+        "linear_fp8w.hip",
     )
 ]
 
