@@ -15,6 +15,26 @@
 //     64 KB V tile per head-group wave — it exceeds the 32 KB L1);
 //   - per-key cache-row offsets staged in LDS once per tile.
 //
+// Loads in flight: a 256-key block is bound by its chain of dependent global
+// round trips, not by bytes, so loads are issued ahead of the arithmetic:
+//   - prologue: one 16-byte q load per thread and the block-table gather of
+//     the first tile are issued together (one round trip instead of three);
+//   - V: a wave keeps V_GROUP keys in flight and loads the next group before
+//     the FMAs of the current one. Slots past the wave's last key are clamped
+//     to that key (a staged row: no unstaged rowoff slot is ever read) and
+//     their FMAs skipped; the loop is peeled so that no load sits behind a
+//     branch (a load that may or may not have been issued makes the compiler
+//     wait with vmcnt(0));
+//   - the in-quad score reduction uses DPP permutes instead of the LDS pipe.
+// Measured and NOT kept (profiles/README.md): prefetching the next 64-key
+// score iteration's K rows into a second register buffer, and issuing the
+// first V group ahead of the softmax (both only cost registers).
+// None of this reorders a floating-point operation: outputs are byte-identical
+// to the kernel before these changes.
+//
+// Workgroup order: rows that share a prompt are made to meet in one XCD's L2
+// (see the remap at the top of the kernel).
+//
 // The kernel is TEMPLATED on the GQA group size: the per-head accumulator
 // array must be statically indexed (a runtime-gqa loop sends it to scratch —
 // cdna guide §5.4 rule 20) and the head loops fully unrolled.
@@ -24,6 +44,8 @@
 
 #include "common.h"
 
+#include <type_traits>
+
 #define TKV ATTN_DECODE_TKV
 #define NTHREADS 256
 #define KLANES 4           // lanes cooperating on one key's dot product
@@ -31,9 +53,31 @@
 
 // partials layout: [B, KVH, max_chunks, gqa, 130]: 128 o values + m + l
 #define PART_STRIDE 130
+#define V_GROUP 16         // V keys a wave keeps in flight per load group
 
+static_assert(TKV == NTHREADS, "one rowoff slot per thread");
+
+// acc[lane] + acc[lane ^ 2], then + the same of lane ^ 1: the 4-lane key
+// group's sum in every lane. DPP quad permutes keep the exchange in the VALU
+// (a __shfl_xor is a ds_bpermute through the LDS pipe).
+__device__ __forceinline__ float quad_sum(float acc) {
+  acc += __int_as_float(__builtin_amdgcn_update_dpp(
+      0, __float_as_int(acc), 0x4E /* quad_perm [2,3,0,1] */, 0xF, 0xF, false));
+  acc += __int_as_float(__builtin_amdgcn_update_dpp(
+      0, __float_as_int(acc), 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, false));
+  return acc;
+}
+
+// o + round(p * v): the product is rounded on its own, never contracted
+__device__ __forceinline__ float mul_then_add(float p, float v, float o) {
+#pragma clang fp contract(off)
+  const float pv = p * v;
+  return o + pv;
+}
+
+// 4 waves/SIMD (at most 128 VGPRs): without the bound <2, fp8> takes 129.
 template <int GQA, bool FP8>
-__global__ __launch_bounds__(NTHREADS) void attn_decode_partial_t(
+__global__ __launch_bounds__(NTHREADS, 4) void attn_decode_partial_t(
     float* __restrict__ partials,
     const bf16_t* __restrict__ q,        // [B, H, 128], row stride q_tstride
     const char* __restrict__ k_cache,    // [NB, KVH, BS, 128], bf16 or fp8
@@ -46,9 +90,31 @@ __global__ __launch_bounds__(NTHREADS) void attn_decode_partial_t(
                                            // the shared-prefix kernel
     float scale, int num_kv_heads,
     int block_size, int max_blocks, int max_chunks, int q_tstride, int chunk_keys) {
-  const int b = blockIdx.x;
-  const int g_kv = blockIdx.y;
-  const int chunk = blockIdx.z;
+  // Workgroups are dealt to the 8 XCDs (each with its own L2) round-robin in
+  // launch order, which puts neighbouring rows on different L2s. Rows that
+  // share a prompt (the n streams of a request) are neighbours in the batch
+  // and read the same K/V blocks, so XCD (launch id % 8) takes a contiguous
+  // eighth of the rows, for every kv head and chunk: sharers meet in one L2.
+  // A bijection of the grid; the rows past a multiple of 8 keep launch order.
+  int b, g_kv, chunk;
+  {
+    const int nb = gridDim.x, ny = gridDim.y;
+    const int nb8 = nb / 8;
+    const int swizzled = nb8 * 8 * ny * (int)gridDim.z;
+    const int lin = blockIdx.x + nb * (blockIdx.y + ny * blockIdx.z);
+    int rest;
+    if (lin < swizzled) {
+      const int idx = lin / 8;
+      b = (lin % 8) * nb8 + idx % nb8;
+      rest = idx / nb8;
+    } else {
+      const int r = lin - swizzled, tail = nb - 8 * nb8;
+      b = 8 * nb8 + r % tail;
+      rest = r / tail;
+    }
+    g_kv = rest % ny;
+    chunk = rest / ny;
+  }
   if (skip_chunks != nullptr && chunk < skip_chunks[b]) return;
   const int L = context_lens[b];
   const int c0 = chunk * chunk_keys;
@@ -67,34 +133,52 @@ __global__ __launch_bounds__(NTHREADS) void attn_decode_partial_t(
   float* ks_lds = reinterpret_cast<float*>(rowoff + TKV);                   // [TKV] (FP8)
   float* vs_lds = ks_lds + TKV;                                             // [TKV] (FP8)
 
-  for (int i = tid; i < GQA * 128; i += NTHREADS) {
-    const int g = i >> 7, d = i & 127;
-    const bf16_t* qp = q + (int64_t)b * q_tstride + (g_kv * GQA + g) * 128;
-    q_lds[i] = bf16_to_f32(((const short*)qp)[d]) * scale;
+  const int* bt = block_tables + (int64_t)b * max_blocks;
+  // stage per-key cache-row element offsets (shared by K and V) and, for
+  // fp8 caches, the per-row dequant scales (scale row index = rowoff/128);
+  // one key per thread
+  auto stage_rowoff = [&](int tile, int nkeys) {
+    if (tid < nkeys) {
+      const int gk = tile + tid;
+      const int64_t off = (((int64_t)bt[gk / block_size] * num_kv_heads + g_kv) * block_size +
+                           (gk % block_size)) * 128;
+      rowoff[tid] = off;
+      if constexpr (FP8) {
+        ks_lds[tid] = k_scale[off >> 7];
+        vs_lds[tid] = v_scale[off >> 7];
+      }
+    }
+  };
+
+  // q: the kv head's GQA x 128 bf16 are contiguous in the row; one 16-byte
+  // load per thread, issued together with the first tile's block-table gather
+  // so the prologue waits once. A row that is not 16-byte aligned takes
+  // 2-byte loads.
+  {
+    const short* qrow =
+        reinterpret_cast<const short*>(q) + (int64_t)b * q_tstride + g_kv * GQA * 128;
+    const bool q_vec = (reinterpret_cast<uintptr_t>(qrow) & 15) == 0;
+    bf16x8_vec qv = {};
+    if (q_vec && tid < GQA * 16) qv = reinterpret_cast<const bf16x8_vec*>(qrow)[tid];
+    stage_rowoff(c0, min(TKV, c1 - c0));
+    if (q_vec) {
+      if (tid < GQA * 16) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) q_lds[tid * 8 + j] = bf16_to_f32(qv[j]) * scale;
+      }
+    } else {
+      for (int i = tid; i < GQA * 128; i += NTHREADS) q_lds[i] = bf16_to_f32(qrow[i]) * scale;
+    }
   }
   if (tid < 8) { mstate[tid] = -INFINITY; lstate[tid] = 0.0f; }
-  __syncthreads();
 
   float o_part[GQA][2];
 #pragma unroll
   for (int g = 0; g < GQA; ++g) { o_part[g][0] = 0.f; o_part[g][1] = 0.f; }
 
-  const int* bt = block_tables + (int64_t)b * max_blocks;
-
   for (int tile = c0; tile < c1; tile += TKV) {
     const int nkeys = min(TKV, c1 - tile);
-    // stage per-key cache-row element offsets (shared by K and V) and, for
-    // fp8 caches, the per-row dequant scales (scale row index = rowoff/128)
-    for (int i = tid; i < nkeys; i += NTHREADS) {
-      const int gk = tile + i;
-      const int64_t off = (((int64_t)bt[gk / block_size] * num_kv_heads + g_kv) * block_size +
-                           (gk % block_size)) * 128;
-      rowoff[i] = off;
-      if constexpr (FP8) {
-        ks_lds[i] = k_scale[off >> 7];
-        vs_lds[i] = v_scale[off >> 7];
-      }
-    }
+    if (tile != c0) stage_rowoff(tile, nkeys);   // the prologue staged the first tile
     __syncthreads();
 
     // ---- scores: KLANES lanes per key, 128/KLANES bf16 per lane -----------
@@ -131,8 +215,7 @@ __global__ __launch_bounds__(NTHREADS) void attn_decode_partial_t(
             float acc = 0.f;
 #pragma unroll
             for (int j = 0; j < ELEMS; ++j) acc += af[j] * qg[j];
-#pragma unroll
-            for (int off = KLANES / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+            acc = quad_sum(acc);
             // fp8: fold the key row's dequant scale into the score (q already
             // carries the softmax scale; s_k is per-key, shared across g)
             if (kl == 0) s_lds[g * TKV + key] = FP8 ? acc * ks_lds[key] : acc;
@@ -171,60 +254,75 @@ __global__ __launch_bounds__(NTHREADS) void attn_decode_partial_t(
 
     // ---- V accumulation (key-partitioned, V read once) --------------------
     {
-      const int kpart = tid >> 6;        // wave id = key partition
-      const int d0 = (tid & 63) * 2;     // this thread's dim pair
 #pragma unroll
       for (int g = 0; g < GQA; ++g) {
         const float alpha = alpha_lds[g];
         o_part[g][0] *= alpha;
         o_part[g][1] *= alpha;
       }
+      const int kpart = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave id = key partition
+      const int d0 = (tid & 63) * 2;     // this thread's dim pair
       const int nk4 = (nkeys + 3) >> 2;
       const int kbeg = kpart * nk4;
       const int kend = min(nkeys, kbeg + nk4);
-      int key = kbeg;
-      // 4 keys in flight: loads issued before use (hides the per-key chain)
-      for (; key + 4 <= kend; key += 4) {
-        uint32_t pairs[4];
+      // keys past kend - 1 are clamped to it: the slot is staged and the row
+      // is one this wave reads anyway
+      auto load_v = [&](uint32_t (&dst)[V_GROUP], int key) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < V_GROUP; ++u) {
+          const int64_t off = rowoff[min(key + u, kend - 1)];
           if constexpr (FP8)
-            pairs[u] = *reinterpret_cast<const unsigned short*>(v_cache + rowoff[key + u] + d0);
+            dst[u] = *reinterpret_cast<const unsigned short*>(v_cache + off + d0);
           else
-            pairs[u] = *reinterpret_cast<const uint32_t*>(v_cache + 2 * (rowoff[key + u] + d0));
+            dst[u] = *reinterpret_cast<const uint32_t*>(v_cache + 2 * (off + d0));
         }
+      };
+      // the group's keys in ascending order; FULL: all V_GROUP slots are
+      // below kend, otherwise the slots at or past kend are skipped (never
+      // multiplied by a zero p: that could flip a signed zero).
+      //
+      // Rounding of o += p * v, kept as this kernel has always computed it so
+      // that outputs stay byte-identical: the accumulation used to run in
+      // blocks of 4 keys from kbeg plus a one-key remainder loop, and the
+      // compiler contracted every multiply-add to an FMA except the LAST
+      // head's inside the 4-key blocks (product rounded, then added). Both
+      // forms are spelled out here, so the result no longer depends on what
+      // the compiler chooses to contract. key - kbeg is a multiple of 4.
+      auto fma_v = [&](auto full, const uint32_t (&pairs)[V_GROUP], int key) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const float vs = FP8 ? vs_lds[key + u] : 1.0f;  // per-row V dequant
-          const float v0 = vs * (FP8 ? fp8_to_f32((unsigned char)(pairs[u] & 0xff))
-                                     : bf16_to_f32((short)(pairs[u] & 0xffff)));
-          const float v1 = vs * (FP8 ? fp8_to_f32((unsigned char)((pairs[u] >> 8) & 0xff))
-                                     : bf16_to_f32((short)(pairs[u] >> 16)));
+        for (int u = 0; u < V_GROUP; ++u) {
+          if (decltype(full)::value || key + u < kend) {   // wave-uniform
+            const bool blk4 = decltype(full)::value || key + (u | 3) < kend;
+            const float vs = FP8 ? vs_lds[key + u] : 1.0f;  // per-row V dequant
+            const float v0 = vs * (FP8 ? fp8_to_f32((unsigned char)(pairs[u] & 0xff))
+                                       : bf16_to_f32((short)(pairs[u] & 0xffff)));
+            const float v1 = vs * (FP8 ? fp8_to_f32((unsigned char)((pairs[u] >> 8) & 0xff))
+                                       : bf16_to_f32((short)(pairs[u] >> 16)));
 #pragma unroll
-          for (int g = 0; g < GQA; ++g) {
-            const float p = s_lds[g * TKV + key + u];  // wave-uniform: LDS broadcast
-            o_part[g][0] += p * v0;
-            o_part[g][1] += p * v1;
+            for (int g = 0; g < GQA; ++g) {
+              const float p = s_lds[g * TKV + key + u];  // wave-uniform: LDS broadcast
+              if (g == GQA - 1 && blk4) {
+                o_part[g][0] = mul_then_add(p, v0, o_part[g][0]);
+                o_part[g][1] = mul_then_add(p, v1, o_part[g][1]);
+              } else {
+                o_part[g][0] = __builtin_fmaf(p, v0, o_part[g][0]);
+                o_part[g][1] = __builtin_fmaf(p, v1, o_part[g][1]);
+              }
+            }
           }
         }
-      }
-      for (; key < kend; ++key) {
-        uint32_t pair;
-        if constexpr (FP8)
-          pair = *reinterpret_cast<const unsigned short*>(v_cache + rowoff[key] + d0);
-        else
-          pair = *reinterpret_cast<const uint32_t*>(v_cache + 2 * (rowoff[key] + d0));
-        const float vs = FP8 ? vs_lds[key] : 1.0f;
-        const float v0 = vs * (FP8 ? fp8_to_f32((unsigned char)(pair & 0xff))
-                                   : bf16_to_f32((short)(pair & 0xffff)));
-        const float v1 = vs * (FP8 ? fp8_to_f32((unsigned char)((pair >> 8) & 0xff))
-                                   : bf16_to_f32((short)(pair >> 16)));
+      };
+      if (kbeg < kend) {   // a wave with an empty quarter loads nothing
+        uint32_t vcur[V_GROUP], vnxt[V_GROUP];
+        load_v(vcur, kbeg);
+        int key = kbeg;
+        for (; key + V_GROUP < kend; key += V_GROUP) {   // a next group exists
+          load_v(vnxt, key + V_GROUP);
+          fma_v(std::true_type{}, vcur, key);
 #pragma unroll
-        for (int g = 0; g < GQA; ++g) {
-          const float p = s_lds[g * TKV + key];
-          o_part[g][0] += p * v0;
-          o_part[g][1] += p * v1;
+          for (int u = 0; u < V_GROUP; ++u) vcur[u] = vnxt[u];
         }
+        fma_v(std::false_type{}, vcur, key);
       }
     }
     __syncthreads();
