@@ -130,10 +130,24 @@ class EngineConfig(BaseModel):
     # streamed per decode step and held in HBM; the freed HBM goes to the KV
     # pool) and run through the weight-only fp8 x bf16 HIP GEMM. embed_tokens
     # and lm_head stay bf16. Below the bf16 numerics, hence opt-in; llama-
-    # family models only, and on the GPU only with dtype="bfloat16". The
+    # family models (Mixtral: together with expert_weight_dtype), and on the
+    # GPU only with dtype="bfloat16". The
     # environment variable KLLMS_WEIGHT_DTYPE=bf16/fp8_e4m3, read once at
     # engine construction, overrides this field.
     weight_dtype: Literal["bf16", "fp8_e4m3"] = "bf16"
+    # MoE (Mixtral) expert weights: "bf16" (default) or "fp8_e4m3": every
+    # layer's stacked experts are quantised at load to OCP e4m3 with one fp32
+    # scale per (expert, output channel), and the bf16 tensors are freed (the
+    # experts are ~96 % of Mixtral-8x7B's parameters; the freed HBM goes to the
+    # KV pool). Decode runs them through the batched weight-only fp8 x bf16 HIP
+    # GEMM, prefill through the fp8 instantiations of the grouped MoE kernels.
+    # The router gate, embed_tokens and lm_head stay as they are. Below the
+    # bf16 numerics, hence opt-in; needs a model with experts, and on the GPU
+    # dtype="bfloat16". Independent of weight_dtype, except that Mixtral with
+    # weight_dtype="fp8_e4m3" needs this field set to "fp8_e4m3" too. The
+    # environment variable KLLMS_EXPERT_WEIGHT_DTYPE=bf16/fp8_e4m3, read once
+    # at engine construction, overrides this field.
+    expert_weight_dtype: Literal["bf16", "fp8_e4m3"] = "bf16"
 
     # Parallelism: TP over RCCL/xGMI (one process per GPU)
     tp_size: int = 1

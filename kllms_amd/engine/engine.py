@@ -203,11 +203,28 @@ class LLMEngine:
         if env_wd not in (None, "", "bf16", "fp8_e4m3"):
             raise ValueError(f"KLLMS_WEIGHT_DTYPE must be bf16 or fp8_e4m3, got {env_wd!r}")
         self.weight_dtype = env_wd or config.weight_dtype
-        if self.weight_dtype == "fp8_e4m3":
-            if self.arch.arch == "mixtral":
+        # fp8 (e4m3) MoE expert weights: config field, overridden by
+        # KLLMS_EXPERT_WEIGHT_DTYPE=bf16/fp8_e4m3 (read once, here)
+        env_ewd = os.environ.get("KLLMS_EXPERT_WEIGHT_DTYPE")
+        if env_ewd not in (None, "", "bf16", "fp8_e4m3"):
+            raise ValueError(
+                f"KLLMS_EXPERT_WEIGHT_DTYPE must be bf16 or fp8_e4m3, got {env_ewd!r}")
+        self.expert_weight_dtype = env_ewd or config.expert_weight_dtype
+        if self.expert_weight_dtype == "fp8_e4m3":
+            if self.arch.num_experts <= 0:
                 raise ValueError(
-                    "weight_dtype='fp8_e4m3' does not cover Mixtral: the expert weights "
-                    "would stay bf16, and a half-quantised model would misstate the saving")
+                    f"expert_weight_dtype='fp8_e4m3' needs a model with experts; "
+                    f"{config.model!r} has none to quantise")
+            if self.device.type == "cuda" and config.dtype != "bfloat16":
+                raise ValueError(
+                    "expert_weight_dtype='fp8_e4m3' on the GPU needs dtype='bfloat16' (the "
+                    f"fp8 GEMMs take bf16 activations), got dtype={config.dtype!r}")
+        if self.weight_dtype == "fp8_e4m3":
+            if self.arch.arch == "mixtral" and self.expert_weight_dtype != "fp8_e4m3":
+                raise ValueError(
+                    "weight_dtype='fp8_e4m3' alone does not cover Mixtral: the expert weights "
+                    "would stay bf16, and a half-quantised model would misstate the saving; "
+                    "set expert_weight_dtype='fp8_e4m3' as well")
             if self.device.type == "cuda" and config.dtype != "bfloat16":
                 raise ValueError(
                     "weight_dtype='fp8_e4m3' on the GPU needs dtype='bfloat16' (the fp8 "
@@ -297,29 +314,40 @@ class LLMEngine:
         else:
             model.to_device(self.device)
             model.random_init_(self.config.seed)
-        if self.weight_dtype == "fp8_e4m3":
+        if "fp8_e4m3" in (self.weight_dtype, self.expert_weight_dtype):
             self._quantize_fp8_weights(model)
         model.eval()
         return model
 
     def _quantize_fp8_weights(self, model) -> None:
-        """Quantise every layer's qkv, o, gate_up and down projection to e4m3
-        with per-channel scales, layer by layer (each bf16 tensor is freed as
-        it goes), and hand all of them ONE bf16 scratch sized for the largest
-        projection: the large-M (packed prefill) path dequantises into it per
-        call, so no bf16 copy of the model is ever kept. embed_tokens and
-        lm_head stay as they are (logit fidelity, tied embeddings)."""
+        """Quantise to e4m3 with per-channel scales, layer by layer (each bf16
+        tensor is freed as it goes): under ``weight_dtype`` every layer's qkv
+        and o projection and a dense MLP's gate_up and down, under
+        ``expert_weight_dtype`` a MoE layer's stacked experts (the router gate
+        stays as it is). The projections share ONE bf16 scratch sized for the
+        largest of them: the large-M (packed prefill) path dequantises into
+        it per call, so no bf16 copy of the model is ever kept; the experts
+        need none (their prefill kernels read e4m3). embed_tokens and lm_head
+        stay as they are (logit fidelity, tied embeddings)."""
         projs = []
         for layer in model.layers:
-            for mod in (layer.self_attn.qkv_proj, layer.self_attn.o_proj,
-                        layer.mlp.gate_up_proj, layer.mlp.down_proj):
+            moe = hasattr(layer.mlp, "w_gate_up")
+            mods = []
+            if self.weight_dtype == "fp8_e4m3":
+                mods += [layer.self_attn.qkv_proj, layer.self_attn.o_proj]
+                if not moe:
+                    mods += [layer.mlp.gate_up_proj, layer.mlp.down_proj]
+            for mod in mods:
                 mod.quantize_fp8_()
                 projs.append(mod)
+            if moe and self.expert_weight_dtype == "fp8_e4m3":
+                layer.mlp.quantize_fp8_()
         if self.device.type == "cuda":
-            scratch = torch.empty(max(m.weight_q.numel() for m in projs),
-                                  dtype=torch.bfloat16, device=self.device)
-            for m in projs:
-                m.fp8_scratch = scratch
+            if projs:
+                scratch = torch.empty(max(m.weight_q.numel() for m in projs),
+                                      dtype=torch.bfloat16, device=self.device)
+                for m in projs:
+                    m.fp8_scratch = scratch
             # return the freed bf16 weights to the driver: _build_kv_cache
             # sizes the KV pool from the HBM that is free
             torch.cuda.empty_cache()

@@ -24,8 +24,10 @@ share prefill batches and decode steps.
 
 from __future__ import annotations
 
+import atexit
 import queue
 import threading
+import weakref
 from concurrent.futures import Future
 from dataclasses import dataclass
 from typing import Dict, List, Optional
@@ -60,6 +62,12 @@ class _PendingPrefill:
     next_pos: int = 0
 
 
+def _shutdown_at_exit(ref) -> None:
+    sched = ref()
+    if sched is not None:
+        sched.shutdown()
+
+
 class BatchScheduler:
     def __init__(self, engine: LLMEngine, admit_wait_s: float = 0.002, engine_lock=None):
         self.engine = engine
@@ -73,6 +81,7 @@ class BatchScheduler:
         self._thread: Optional[threading.Thread] = None
         self._lock = threading.Lock()
         self._stop = threading.Event()
+        self._atexit_registered = False
         # observability
         self.steps = 0
         self.admitted_batches = 0
@@ -113,6 +122,12 @@ class BatchScheduler:
                 self._stop.clear()
                 self._thread = threading.Thread(target=self._loop, name="kllms-scheduler", daemon=True)
                 self._thread.start()
+                if not self._atexit_registered:
+                    # join the worker before the interpreter finalizes: a daemon
+                    # thread that wakes during finalization is killed mid-frame,
+                    # which can abort the process at exit
+                    self._atexit_registered = True
+                    atexit.register(_shutdown_at_exit, weakref.ref(self))
 
     def _drain(self, active_streams: int, block: bool) -> List[_Ticket]:
         """Admit pending tickets up to the engine's stream budget.

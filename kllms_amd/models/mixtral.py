@@ -11,6 +11,11 @@ all experts (same HBM traffic as routed compute when nearly every expert is
 touched; hipGraph-friendly because shapes are data-independent), prefill
 shapes bucket tokens per expert and run grouped GEMMs.
 
+Opt-in fp8 (e4m3) expert weights (``quantize_fp8_``): the stacked tensors are
+replaced by e4m3 buffers with one fp32 scale per (expert, output channel); the
+dense path runs the batched weight-only fp8 GEMM, the grouped path the fp8
+instantiations of the grouped kernels. No bf16 copy of the experts is kept.
+
 Router semantics match Mixtral: softmax over ALL expert logits (fp32), top-k
 (default 2), renormalize the selected weights.
 """
@@ -18,9 +23,11 @@ Router semantics match Mixtral: softmax over ALL expert logits (fp32), top-k
 from __future__ import annotations
 
 import torch
+import torch.distributed as dist
 import torch.nn as nn
 
 from .. import ops
+from ..ops import torch_ref
 from ..engine.config import ModelArchConfig
 from ..parallel.tp import ParallelContext
 from .llama import LlamaDecoderLayer, LlamaForCausalLM
@@ -53,6 +60,37 @@ class MixtralMoE(nn.Module):
         else:
             self.w_down.data[e].copy_(t.to(self.w_down.dtype))
 
+    def quantize_fp8_(self) -> None:
+        """Opt-in fp8 (e4m3) expert weights: ``w_gate_up`` / ``w_down`` become
+        the buffers ``w_gate_up_q`` / ``w_down_q`` (e4m3, same shapes) with
+        ``w_gate_up_scale`` [E, 2I] / ``w_down_scale`` [E, H] (fp32, one scale
+        per expert and output channel), and the bf16 tensors are freed.
+        gate_up's output channels are whole on every rank; w_down's K is
+        sharded, so its per-row amax is all-reduced (MAX) first and each rank
+        holds the matching slice of the TP=1 quantisation. Expert by expert,
+        so the fp32 temporaries stay at one expert's size."""
+        if self.w_gate_up is None:
+            return  # already quantised
+        for name in ("w_gate_up", "w_down"):
+            w = getattr(self, name).data
+            amax = torch.stack([w[e].float().abs().amax(dim=1) for e in range(self.E)])
+            if name == "w_down" and self.ctx.world_size > 1:
+                dist.all_reduce(amax, op=dist.ReduceOp.MAX, group=self.ctx.group)
+            q = torch.empty(w.shape, dtype=torch.float8_e4m3fn, device=w.device)
+            scale = torch.empty_like(amax)
+            for e in range(self.E):
+                qe, se = ops.quantize_fp8_rows(w[e], amax[e])
+                q[e].view(torch.uint8).copy_(qe.view(torch.uint8))
+                scale[e].copy_(se)
+            del w
+            setattr(self, name, None)  # drops the Parameter; the bf16 storage is freed here
+            self.register_buffer(name + "_q", q, persistent=False)
+            self.register_buffer(name + "_scale", scale, persistent=False)
+
+    @property
+    def quantized(self) -> bool:
+        return self.w_gate_up is None
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         T, H = x.shape
         router_logits = self.gate(x).float()                       # [T, E]
@@ -62,7 +100,9 @@ class MixtralMoE(nn.Module):
 
         if T <= 8 * self.E:
             out = self._forward_dense(x, topw, topi)
-        elif x.is_cuda:
+        elif x.is_cuda and not (self.quantized and ops._force_torch()):
+            # (quantised experts under KLLMS_AMD_FORCE_TORCH_OPS=1 take the
+            # torch loop, the reference the fp8 kernels are tested against)
             out = self._forward_grouped_hip(x, topw, topi)
         else:
             out = self._forward_grouped(x, topw, topi)
@@ -75,10 +115,18 @@ class MixtralMoE(nn.Module):
         routing, needs no token bucketing, and replays cleanly in a hipGraph
         (no data-dependent shapes)."""
         T = x.shape[0]
-        xb = x.unsqueeze(0).expand(self.E, T, -1)                     # [E, T, H]
-        gu2 = torch.bmm(xb, self.w_gate_up.transpose(1, 2)).view(self.E * T, 2 * self.I)
+        if self.quantized:
+            # x is shared by all experts (batch stride 0), act is per expert
+            gu2 = ops.linear_fp8w_batched(x, self.w_gate_up_q, self.w_gate_up_scale)
+        else:
+            xb = x.unsqueeze(0).expand(self.E, T, -1)                 # [E, T, H]
+            gu2 = torch.bmm(xb, self.w_gate_up.transpose(1, 2))
+        gu2 = gu2.view(self.E * T, 2 * self.I)
         act = ops.silu_mul(gu2[:, : self.I], gu2[:, self.I:]).view(self.E, T, self.I)
-        ye = torch.bmm(act, self.w_down.transpose(1, 2))              # [E, T, H]
+        if self.quantized:
+            ye = ops.linear_fp8w_batched(act, self.w_down_q, self.w_down_scale)
+        else:
+            ye = torch.bmm(act, self.w_down.transpose(1, 2))          # [E, T, H]
         # combine: weight[e, t] = topw where topi == e else 0
         w = torch.zeros(self.E, T, device=x.device, dtype=torch.float32)
         w.scatter_(0, topi.t().long(), topw.t().float())
@@ -123,8 +171,13 @@ class MixtralMoE(nn.Module):
         act = torch.empty(S, self.I, device=dev, dtype=x.dtype)
         y = torch.empty(S, H, device=dev, dtype=x.dtype)
         pad_off32 = pad_off.to(torch.int32)
-        ops.moe_gateup(act, x, self.w_gate_up, sorted_ids, pad_off32, self._zeros_page)
-        ops.moe_down(y, act, self.w_down, pad_off32)
+        if self.quantized:
+            ops.moe_gateup(act, x, self.w_gate_up_q, sorted_ids, pad_off32, self._zeros_page,
+                           scale=self.w_gate_up_scale)
+            ops.moe_down(y, act, self.w_down_q, pad_off32, scale=self.w_down_scale)
+        else:
+            ops.moe_gateup(act, x, self.w_gate_up, sorted_ids, pad_off32, self._zeros_page)
+            ops.moe_down(y, act, self.w_down, pad_off32)
 
         valid = sorted_ids >= 0
         out = torch.zeros(T, H, device=dev, dtype=torch.float32)
@@ -147,9 +200,15 @@ class MixtralMoE(nn.Module):
                 continue
             toks = flat_tok[sel]
             xe = x[toks]
-            gu = torch.nn.functional.linear(xe, self.w_gate_up[e])
+            if self.quantized:
+                gu = torch_ref.linear_fp8w(xe, self.w_gate_up_q[e], self.w_gate_up_scale[e])
+            else:
+                gu = torch.nn.functional.linear(xe, self.w_gate_up[e])
             g, u = gu.split([self.I, self.I], dim=-1)
-            ye = torch.nn.functional.linear(ops.silu_mul(g, u), self.w_down[e])
+            if self.quantized:
+                ye = torch_ref.linear_fp8w(ops.silu_mul(g, u), self.w_down_q[e], self.w_down_scale[e])
+            else:
+                ye = torch.nn.functional.linear(ops.silu_mul(g, u), self.w_down[e])
             out.index_add_(0, toks, ye * flat_w[sel].unsqueeze(-1).to(ye.dtype))
         return out
 

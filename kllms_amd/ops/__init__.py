@@ -131,6 +131,42 @@ def linear_fp8w(
     return torch_ref.linear_fp8w(x, q, scale, bias)
 
 
+def _fp8w_batched_kernel_takes(x: torch.Tensor, E: int, N: int, K: int) -> bool:
+    rows = x if x.dim() == 2 else x[0]
+    return (_fp8w_kernel_takes(rows, N, K) and 1 <= E <= 1024
+            and (x.dim() == 2 or x.stride(0) % 8 == 0))
+
+
+def linear_fp8w_batched(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """``out[e] = (x_e @ q[e]^T) * scale[e]`` for the E experts of a MoE layer:
+    ``q`` e4m3 [E, N, K], ``scale`` fp32 [E, N]; ``x`` is [M, K] (one
+    activation shared by all experts) or [E, M, K] (one per expert). Returns
+    [E, M, N] in the dtype of ``x``.
+
+    On the GPU, bf16 ``x`` with 1 <= M <= 256, K % 64 == 0 and N % 16 == 0 runs
+    ONE batched launch of the ``linear_fp8w`` kernel (expert index in the
+    grid); at E = 1 it gives the bits of ``linear_fp8w``. Anything else
+    dequantises the experts to bf16 and runs ``torch.bmm``, like the large-M
+    branch of ``linear_fp8w``."""
+    E, N, K = q.shape
+    if x.is_cuda and not _force_torch():
+        C = _hip_or_raise()
+        if x.dtype != torch.bfloat16:
+            raise ValueError(f"linear_fp8w_batched on GPU needs bf16 activations, got {x.dtype}")
+        if _fp8w_batched_kernel_takes(x, E, N, K):
+            out = torch.empty((E, x.shape[-2], N), dtype=torch.bfloat16, device=x.device)
+            C.linear_fp8w_batched(out, x, q, scale)
+            return out
+        if K % 16 == 0:
+            w = torch.empty((E, N, K), dtype=torch.bfloat16, device=x.device)
+            C.dequant_fp8w(w, q.view(E * N, K), scale.view(E * N))
+        else:       # the dequant kernel converts 16 weights per thread
+            w = (q.float() * scale.unsqueeze(-1)).bfloat16()
+        xb = x.unsqueeze(0).expand(E, -1, -1) if x.dim() == 2 else x
+        return torch.bmm(xb, w.transpose(1, 2))
+    return torch_ref.linear_fp8w_batched(x, q, scale)
+
+
 def store_kv(
     k: torch.Tensor,
     v: torch.Tensor,
@@ -316,6 +352,11 @@ def sample_fsm(
                                 fsm_state, tables)
 
 
+def _scale_or_empty(scale: Optional[torch.Tensor], device: torch.device) -> torch.Tensor:
+    """The binding takes an empty tensor for 'bf16 weights, no scales'."""
+    return scale if scale is not None else torch.empty(0, dtype=torch.float32, device=device)
+
+
 def moe_gateup(
     act: torch.Tensor,
     x: torch.Tensor,
@@ -323,11 +364,14 @@ def moe_gateup(
     sorted_ids: torch.Tensor,
     pad_offsets: torch.Tensor,
     zeros: torch.Tensor,
+    scale: Optional[torch.Tensor] = None,
 ) -> None:
     """Grouped MoE gate/up GEMM + fused silu*mul into `act` (sorted-by-expert
     row space). GPU-only (Mixtral prefill hot path); the CPU path keeps the
-    per-expert torch loop in models/mixtral.py."""
-    _hip_or_raise().moe_gateup(act, x, w_gate_up, sorted_ids, pad_offsets, zeros)
+    per-expert torch loop in models/mixtral.py. With ``scale`` (fp32
+    [E, 2*IN]) ``w_gate_up`` is e4m3 and the fp8 instantiation runs."""
+    _hip_or_raise().moe_gateup(act, x, w_gate_up, _scale_or_empty(scale, x.device),
+                               sorted_ids, pad_offsets, zeros)
 
 
 def moe_down(
@@ -335,9 +379,11 @@ def moe_down(
     act: torch.Tensor,
     w_down: torch.Tensor,
     pad_offsets: torch.Tensor,
+    scale: Optional[torch.Tensor] = None,
 ) -> None:
-    """Grouped MoE down GEMM in sorted-row space (see moe_gateup)."""
-    _hip_or_raise().moe_down(y, act, w_down, pad_offsets)
+    """Grouped MoE down GEMM in sorted-row space (see moe_gateup); ``scale``
+    (fp32 [E, H]) goes with e4m3 ``w_down``."""
+    _hip_or_raise().moe_down(y, act, w_down, _scale_or_empty(scale, act.device), pad_offsets)
 
 
 def levenshtein_pairs(

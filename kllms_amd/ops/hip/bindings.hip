@@ -303,17 +303,35 @@ void one_shot_allreduce(std::vector<torch::Tensor> bufs) {
 }
 
 // --- grouped MoE expert GEMMs (moe.hip) --------------------------------------
-extern "C" void launch_moe_gateup(void* act, const void* x, const void* w,
+extern "C" void launch_moe_gateup(void* act, const void* x, const void* w, const float* scale,
                                   const int* sorted_ids, const int* pad_offsets,
                                   const void* zeros, int E, int IN, int K,
                                   hipStream_t stream);
-extern "C" void launch_moe_down(void* y, const void* act, const void* w,
+extern "C" void launch_moe_down(void* y, const void* act, const void* w, const float* scale,
                                 const int* pad_offsets, int E, int H, int IN,
                                 hipStream_t stream);
 
-void moe_gateup(torch::Tensor act, torch::Tensor x, torch::Tensor w,
+// Expert weights [E, N, K]: bf16 with an empty `scale`, or e4m3 with fp32
+// per-channel scales [E, N]. Returns the scale pointer (nullptr for bf16).
+static const float* moe_weight_scale(const torch::Tensor& w, const torch::Tensor& scale) {
+  TORCH_CHECK(w.is_cuda() && w.is_contiguous() && w.dim() == 3, "expert weights must be contiguous [E, N, K] on GPU");
+  if (scale.numel() == 0) {
+    TORCH_CHECK(w.scalar_type() == at::kBFloat16, "expert weights without scales must be bf16");
+    return nullptr;
+  }
+  TORCH_CHECK(w.scalar_type() == at::kFloat8_e4m3fn, "expert weights with scales must be e4m3");
+  TORCH_CHECK(scale.is_cuda() && scale.is_contiguous() && scale.scalar_type() == at::kFloat &&
+              scale.dim() == 2 && scale.size(0) == w.size(0) && scale.size(1) == w.size(1),
+              "expert scales must be contiguous fp32 [E, N] on GPU");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              "e4m3 expert weights must be 16-byte aligned");
+  return scale.data_ptr<float>();
+}
+
+void moe_gateup(torch::Tensor act, torch::Tensor x, torch::Tensor w, torch::Tensor scale,
                 torch::Tensor sorted_ids, torch::Tensor pad_offsets, torch::Tensor zeros) {
-  CHECK_BF16_CONTIG(act); CHECK_BF16_CONTIG(x); CHECK_BF16_CONTIG(w); CHECK_BF16_CONTIG(zeros);
+  CHECK_BF16_CONTIG(act); CHECK_BF16_CONTIG(x); CHECK_BF16_CONTIG(zeros);
+  const float* sc = moe_weight_scale(w, scale);
   TORCH_CHECK(sorted_ids.scalar_type() == at::kInt && pad_offsets.scalar_type() == at::kInt,
               "routing tensors must be int32");
   const int E = w.size(0);
@@ -323,20 +341,22 @@ void moe_gateup(torch::Tensor act, torch::Tensor x, torch::Tensor w,
   TORCH_CHECK(act.size(1) == IN && x.size(1) == K && zeros.numel() >= K);
   TORCH_CHECK(act.size(0) % 128 == 0, "sorted rows must be padded to 128");
   TORCH_CHECK(pad_offsets.numel() == E + 1);
-  launch_moe_gateup(act.data_ptr(), x.data_ptr(), w.data_ptr(),
+  launch_moe_gateup(act.data_ptr(), x.data_ptr(), w.data_ptr(), sc,
                     sorted_ids.data_ptr<int>(), pad_offsets.data_ptr<int>(),
                     zeros.data_ptr(), E, IN, K, cur_stream());
 }
 
-void moe_down(torch::Tensor y, torch::Tensor act, torch::Tensor w, torch::Tensor pad_offsets) {
-  CHECK_BF16_CONTIG(y); CHECK_BF16_CONTIG(act); CHECK_BF16_CONTIG(w);
+void moe_down(torch::Tensor y, torch::Tensor act, torch::Tensor w, torch::Tensor scale,
+              torch::Tensor pad_offsets) {
+  CHECK_BF16_CONTIG(y); CHECK_BF16_CONTIG(act);
+  const float* sc = moe_weight_scale(w, scale);
   const int E = w.size(0);
   const int H = w.size(1);
   const int IN = w.size(2);
   TORCH_CHECK(H % 64 == 0 && IN % 64 == 0, "H % 64, IN % 64 required");
   TORCH_CHECK(y.size(1) == H && act.size(1) == IN);
   TORCH_CHECK(pad_offsets.numel() == E + 1);
-  launch_moe_down(y.data_ptr(), act.data_ptr(), w.data_ptr(),
+  launch_moe_down(y.data_ptr(), act.data_ptr(), w.data_ptr(), sc,
                   pad_offsets.data_ptr<int>(), E, H, IN, cur_stream());
 }
 
@@ -400,6 +420,12 @@ extern "C" void launch_linear_fp8w(void* out, float* slabs, const void* x, const
                                    long x_stride, int mt, int splitk, hipStream_t stream);
 extern "C" void launch_dequant_fp8w(void* w, const void* q, const float* scale, long numel,
                                     int K, hipStream_t stream);
+extern "C" void linear_fp8w_batched_plan(int E, int M, int N, int K, int n_cus, int* mt,
+                                         int* splitk);
+extern "C" void launch_linear_fp8w_batched(void* out, float* slabs, const void* x,
+                                           const void* q, const float* scale, int E, int M,
+                                           int N, int K, long x_stride, long x_bstride, int mt,
+                                           int splitk, hipStream_t stream);
 
 #define CHECK_FP8W(q, scale)                                                             \
   TORCH_CHECK((q).is_cuda() && (q).is_contiguous() && (q).dim() == 2 &&                  \
@@ -451,6 +477,53 @@ void linear_fp8w(torch::Tensor out, torch::Tensor x, torch::Tensor q, torch::Ten
                      bptr, (int)M, (int)N, (int)K, (long)x.stride(0), mt, splitk, cur_stream());
 }
 
+// out[e] = bf16((x_e @ q[e]^T) * scale[e]) for the E experts of q [E, N, K]; x is
+// [M, K] (shared by all experts) or [E, M, K], unit inner stride, row and batch
+// strides multiples of 8 elements. Same shape limits as linear_fp8w.
+void linear_fp8w_batched(torch::Tensor out, torch::Tensor x, torch::Tensor q,
+                         torch::Tensor scale) {
+  TORCH_CHECK(q.is_cuda() && q.is_contiguous() && q.dim() == 3 &&
+              q.scalar_type() == at::kFloat8_e4m3fn,
+              "linear_fp8w_batched: q must be contiguous e4m3 [E, N, K] on GPU");
+  const int64_t E = q.size(0), N = q.size(1), K = q.size(2);
+  TORCH_CHECK(scale.is_cuda() && scale.is_contiguous() && scale.scalar_type() == at::kFloat &&
+              scale.dim() == 2 && scale.size(0) == E && scale.size(1) == N,
+              "linear_fp8w_batched: scale must be contiguous fp32 [E, N] on GPU");
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && (x.dim() == 2 || x.dim() == 3),
+              "linear_fp8w_batched: x must be bf16 [M, K] or [E, M, K] on GPU");
+  const bool shared = x.dim() == 2;
+  const int64_t M = x.size(shared ? 0 : 1);
+  const int64_t x_stride = x.stride(shared ? 0 : 1);
+  const int64_t x_bstride = shared ? 0 : x.stride(0);
+  TORCH_CHECK(x.size(-1) == K && (shared || x.size(0) == E),
+              "linear_fp8w_batched: x and q disagree on E or K");
+  TORCH_CHECK(E >= 1 && E <= 1024 && M >= 1 && M <= 256 && K % 64 == 0 && N % 16 == 0,
+              "linear_fp8w_batched: needs 1 <= E <= 1024, 1 <= M <= 256, K % 64 == 0, "
+              "N % 16 == 0; got E=", E, " M=", M, " N=", N, " K=", K);
+  TORCH_CHECK(x.stride(-1) == 1 && x_stride >= K && x_stride % 8 == 0 && x_bstride % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "linear_fp8w_batched: x needs unit inner stride and 16-byte-aligned rows and experts");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kBFloat16 && out.is_contiguous() &&
+              out.dim() == 3 && out.size(0) == E && out.size(1) == M && out.size(2) == N,
+              "linear_fp8w_batched: out must be contiguous bf16 [E, M, N]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(scale.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(out.data_ptr()) % 8 == 0,
+              "linear_fp8w_batched: q/scale must be 16-byte aligned, out 8-byte aligned");
+  const int n_cus = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  int mt = 1, splitk = 1;
+  linear_fp8w_batched_plan((int)E, (int)M, (int)N, (int)K, n_cus, &mt, &splitk);
+  float* slabs = nullptr;
+  torch::Tensor ws;
+  if (splitk > 1) {
+    ws = torch::empty({E * splitk * M * N}, torch::dtype(torch::kFloat).device(x.device()));
+    slabs = ws.data_ptr<float>();
+  }
+  launch_linear_fp8w_batched(out.data_ptr(), slabs, x.data_ptr(), q.data_ptr(),
+                             scale.data_ptr<float>(), (int)E, (int)M, (int)N, (int)K,
+                             (long)x_stride, (long)x_bstride, mt, splitk, cur_stream());
+}
+
 // w[N, K] = bf16(fp32(q) * scale[n]) into the first N*K elements of `w` (a
 // reusable bf16 scratch); K % 16 == 0.
 void dequant_fp8w(torch::Tensor w, torch::Tensor q, torch::Tensor scale) {
@@ -468,6 +541,7 @@ void dequant_fp8w(torch::Tensor w, torch::Tensor q, torch::Tensor scale) {
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_fp8w", &linear_fp8w);
+  m.def("linear_fp8w_batched", &linear_fp8w_batched);
   m.def("dequant_fp8w", &dequant_fp8w);
   m.def("levenshtein_pairs", &levenshtein_pairs);
   m.def("moe_gateup", &moe_gateup);

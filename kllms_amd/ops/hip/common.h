@@ -93,6 +93,21 @@ __device__ __forceinline__ unsigned char f32_to_fp8(float f) {
   return v.__x;
 }
 
+// weight-only fp8 (linear_fp8w.hip, the fp8 grouped MoE kernels of moe.hip)
+typedef float fw_f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int fw_u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int fw_u32x2 __attribute__((ext_vector_type(2)));
+
+// 4 e4m3 bytes of one dword -> 4 bf16 in two dwords (byte 0 lowest). The
+// hardware conversion gives the exact fp32 value; its low 16 bits are zero,
+// so taking the high half is the exact bf16.
+__device__ __forceinline__ void fw_cvt4(uint32_t w, uint32_t& lo, uint32_t& hi) {
+  const fw_f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+  const fw_f32x2 b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+  lo = (__float_as_uint(a[0]) >> 16) | (__float_as_uint(a[1]) & 0xffff0000u);
+  hi = (__float_as_uint(b[0]) >> 16) | (__float_as_uint(b[1]) & 0xffff0000u);
+}
+
 // splitmix64: per-(seed, step, token) counter-based RNG for the sampler
 __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
   x += 0x9E3779B97F4A7C15ULL;

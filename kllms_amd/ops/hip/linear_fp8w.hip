@@ -36,6 +36,11 @@
 // a second launch sums the slabs in slice order and applies scale and bias.
 // No atomics, no counters: the same call gives the same bits, and both
 // launches are plain stream work (hipGraph-capturable).
+//
+// Batched form (the experts of a MoE layer): E such problems in one launch,
+//   out[e, m, n] = bf16( (sum_k x_e[m, k] * q[e, n, k]) * scale[e, n] ),
+// the same body per block with the expert index in the grid and per-expert
+// offsets on x (0 = shared), q, scale, out and the slabs; no bias.
 
 #include <algorithm>
 
@@ -47,19 +52,6 @@
 #define FW_RING 4                // register ring slots (> prefetch depth, even)
 
 typedef __bf16 fw_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float fw_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int fw_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int fw_u32x2 __attribute__((ext_vector_type(2)));
-
-// 4 e4m3 bytes of one dword -> 4 bf16 in two dwords (byte 0 lowest). The
-// hardware conversion gives the exact fp32 value; its low 16 bits are zero,
-// so taking the high half is the exact bf16.
-__device__ __forceinline__ void fw_cvt4(uint32_t w, uint32_t& lo, uint32_t& hi) {
-  const fw_f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
-  const fw_f32x2 b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
-  lo = (__float_as_uint(a[0]) >> 16) | (__float_as_uint(a[1]) & 0xffff0000u);
-  hi = (__float_as_uint(b[0]) >> 16) | (__float_as_uint(b[1]) & 0xffff0000u);
-}
 
 __device__ __forceinline__ uint32_t fw_pack2(float a, float b) {
   return (uint32_t)(uint16_t)f32_to_bf16(a) | ((uint32_t)(uint16_t)f32_to_bf16(b) << 16);
@@ -67,15 +59,16 @@ __device__ __forceinline__ uint32_t fw_pack2(float a, float b) {
 
 // MT: 32-row activation tiles per block (1, 2 or 4). SPLIT: write the raw
 // fp32 accumulators to this K slice's slab instead of the bf16 output.
+// The body of both kernels below: one [M, N, K] problem, K slice ks.
 template <int MT, bool SPLIT>
-__global__ void __launch_bounds__(256) linear_fp8w_kernel(
+__device__ __forceinline__ void fw_body(
     bf16_t* __restrict__ out,            // [M, N]
     float* __restrict__ slabs,           // [splitk, M, N] (SPLIT only)
     const bf16_t* __restrict__ x,        // [M, K], row stride x_stride
     const unsigned char* __restrict__ q, // [N, K]
     const float* __restrict__ scale,     // [N]
     const bf16_t* __restrict__ bias,     // [N] or nullptr
-    int M, int N, int K, long x_stride, int stages_per_slice) {
+    int M, int N, int K, long x_stride, int stages_per_slice, int ks) {
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wv = tid >> 6;
@@ -84,7 +77,6 @@ __global__ void __launch_bounds__(256) linear_fp8w_kernel(
 
   const int n_blk = blockIdx.x * FW_BN + wv * 32;   // first column of this wave
   const int m_base = blockIdx.y * (MT * 32);
-  const int ks = blockIdx.z;
 
   const int n_stages = K / FW_BK;
   const int s_begin = ks * stages_per_slice;
@@ -210,7 +202,39 @@ __global__ void __launch_bounds__(256) linear_fp8w_kernel(
   }
 }
 
-// out[m, n] = bf16( (slab[0] + slab[1] + ... in slice order) * scale + bias )
+template <int MT, bool SPLIT>
+__global__ void __launch_bounds__(256) linear_fp8w_kernel(
+    bf16_t* __restrict__ out, float* __restrict__ slabs, const bf16_t* __restrict__ x,
+    const unsigned char* __restrict__ q, const float* __restrict__ scale,
+    const bf16_t* __restrict__ bias, int M, int N, int K, long x_stride,
+    int stages_per_slice) {
+  fw_body<MT, SPLIT>(out, slabs, x, q, scale, bias, M, N, K, x_stride, stages_per_slice,
+                     blockIdx.z);
+}
+
+// E independent [M, N, K] problems (the experts of a MoE layer) in one launch:
+// blockIdx.z = e * splitk + ks. Expert e owns out[e] [M, N], q[e] [N, K],
+// scale[e] [N], its splitk slabs and x + e * x_bstride (x_bstride == 0: one
+// activation shared by all experts). Every clamp of the body is against M and
+// N of expert e's own tensors, so a block never reads or writes a neighbour's.
+template <int MT, bool SPLIT>
+__global__ void __launch_bounds__(256) linear_fp8w_batched_kernel(
+    bf16_t* __restrict__ out,            // [E, M, N]
+    float* __restrict__ slabs,           // [E, splitk, M, N] (SPLIT only)
+    const bf16_t* __restrict__ x,        // rows x_stride apart, experts x_bstride apart
+    const unsigned char* __restrict__ q, // [E, N, K]
+    const float* __restrict__ scale,     // [E, N]
+    int M, int N, int K, long x_stride, long x_bstride, int stages_per_slice, int splitk) {
+  const int e = blockIdx.z / splitk;
+  const int ks = blockIdx.z - e * splitk;
+  const long MN = (long)M * N;
+  fw_body<MT, SPLIT>(out + e * MN, slabs + (long)e * splitk * MN, x + e * x_bstride,
+                     q + (long)e * N * K, scale + (long)e * N, nullptr, M, N, K, x_stride,
+                     stages_per_slice, ks);
+}
+
+// out[m, n] = bf16( (slab[0] + slab[1] + ... in slice order) * scale + bias );
+// blockIdx.y is the expert of a batched call (0 otherwise).
 extern "C" __global__ void __launch_bounds__(256) linear_fp8w_reduce_kernel(
     bf16_t* __restrict__ out, const float* __restrict__ slabs,
     const float* __restrict__ scale, const bf16_t* __restrict__ bias,
@@ -218,6 +242,9 @@ extern "C" __global__ void __launch_bounds__(256) linear_fp8w_reduce_kernel(
   const long i4 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
   if (i4 >= MN) return;
   const int n = (int)(i4 % N);
+  out += blockIdx.y * MN;
+  slabs += (long)blockIdx.y * splitk * MN;
+  scale += (long)blockIdx.y * N;
   f32x4 s = *reinterpret_cast<const f32x4*>(slabs + i4);
   for (int k = 1; k < splitk; ++k) {
     const f32x4 t = *reinterpret_cast<const f32x4*>(slabs + (long)k * MN + i4);
@@ -260,15 +287,15 @@ extern "C" __global__ void __launch_bounds__(256) dequant_fp8w_kernel(
   }
 }
 
-// Split-K slices for an [M, N, K] call with 32*mt-row blocks. Fills the CUs
+// Split-K slices for E [M, N, K] problems with 32*mt-row blocks. Fills the CUs
 // when there are few column tiles, but keeps the fp32 slab traffic
-// (splitk * M * N * 4 B) under half the weight bytes (N * K).
-static int fw_splitk(int mt, int M, int N, int K, int n_cus) {
+// (splitk * M * N * 4 B per problem) under half the weight bytes (N * K).
+static int fw_splitk(int mt, int E, int M, int N, int K, int n_cus) {
   const int m_blocks = (M + 32 * mt - 1) / (32 * mt);
   const int n_tiles = (N + FW_BN - 1) / FW_BN;
   const int n_stages = K / FW_BK;
   const int per_cu = mt == 4 ? 2 : 4;               // resident blocks wanted per CU
-  int want = (n_cus * per_cu) / (n_tiles * m_blocks);
+  int want = (int)(((long)n_cus * per_cu) / ((long)n_tiles * m_blocks * E));
   const int cap = K / (8 * M);                      // slab bytes <= weight bytes / 2
   want = std::min(std::min(want, cap), std::min(n_stages, 16));
   if (want <= 1) return 1;
@@ -276,23 +303,28 @@ static int fw_splitk(int mt, int M, int N, int K, int n_cus) {
   return (n_stages + per - 1) / per;                // no empty slice
 }
 
-// Row tile (mt) and split-K of a call: a pure function of the shape and the
-// CU count, so the result bits never depend on anything else. M > 64 takes
-// 128-row blocks unless that grid leaves CUs idle; then 64-row blocks give
-// twice the blocks at half the MFMA and LDS work each (the second row block
-// re-reads the weights through L2).
-extern "C" void linear_fp8w_plan(int M, int N, int K, int n_cus, int* mt_out, int* splitk_out) {
+// Row tile (mt) and split-K of a call: a pure function of the shape, the
+// number of problems and the CU count, so the result bits never depend on
+// anything else. M > 64 takes 128-row blocks unless that grid leaves CUs idle;
+// then 64-row blocks give twice the blocks at half the MFMA and LDS work each
+// (the second row block re-reads the weights through L2).
+extern "C" void linear_fp8w_batched_plan(int E, int M, int N, int K, int n_cus, int* mt_out,
+                                         int* splitk_out) {
   int mt = M <= 32 ? 1 : (M <= 64 ? 2 : 4);
-  int splitk = fw_splitk(mt, M, N, K, n_cus);
+  int splitk = fw_splitk(mt, E, M, N, K, n_cus);
   if (mt == 4) {
-    const int blocks = ((N + FW_BN - 1) / FW_BN) * ((M + 127) / 128) * splitk;
+    const long blocks = (long)((N + FW_BN - 1) / FW_BN) * ((M + 127) / 128) * splitk * E;
     if (blocks < n_cus) {
       mt = 2;
-      splitk = fw_splitk(mt, M, N, K, n_cus);
+      splitk = fw_splitk(mt, E, M, N, K, n_cus);
     }
   }
   *mt_out = mt;
   *splitk_out = splitk;
+}
+
+extern "C" void linear_fp8w_plan(int M, int N, int K, int n_cus, int* mt_out, int* splitk_out) {
+  linear_fp8w_batched_plan(1, M, N, K, n_cus, mt_out, splitk_out);
 }
 
 extern "C" void launch_linear_fp8w(void* out, float* slabs, const void* x, const void* q,
@@ -311,6 +343,30 @@ extern "C" void launch_linear_fp8w(void* out, float* slabs, const void* x, const
     const int blocks = (int)((MN / 4 + 255) / 256);
     hipLaunchKernelGGL(linear_fp8w_reduce_kernel, dim3(blocks), dim3(256), 0, stream,
                        (bf16_t*)out, (const float*)slabs, scale, (const bf16_t*)bias,
+                       MN, N, splitk);
+  } else {
+    if (mt == 1) FW_LAUNCH(1, false); else if (mt == 2) FW_LAUNCH(2, false); else FW_LAUNCH(4, false);
+  }
+#undef FW_LAUNCH
+}
+
+extern "C" void launch_linear_fp8w_batched(void* out, float* slabs, const void* x,
+                                           const void* q, const float* scale, int E, int M,
+                                           int N, int K, long x_stride, long x_bstride, int mt,
+                                           int splitk, hipStream_t stream) {
+  const int n_stages = K / FW_BK;
+  const int per = (n_stages + splitk - 1) / splitk;
+  const dim3 grid((N + FW_BN - 1) / FW_BN, (M + 32 * mt - 1) / (32 * mt), E * splitk);
+#define FW_LAUNCH(MT_, SPLIT_)                                                              \
+  hipLaunchKernelGGL((linear_fp8w_batched_kernel<MT_, SPLIT_>), grid, dim3(256), 0, stream, \
+                     (bf16_t*)out, slabs, (const bf16_t*)x, (const unsigned char*)q, scale, \
+                     M, N, K, x_stride, x_bstride, per, splitk)
+  if (splitk > 1) {
+    if (mt == 1) FW_LAUNCH(1, true); else if (mt == 2) FW_LAUNCH(2, true); else FW_LAUNCH(4, true);
+    const long MN = (long)M * N;
+    const int blocks = (int)((MN / 4 + 255) / 256);
+    hipLaunchKernelGGL(linear_fp8w_reduce_kernel, dim3(blocks, E), dim3(256), 0, stream,
+                       (bf16_t*)out, (const float*)slabs, scale, (const bf16_t*)nullptr,
                        MN, N, splitk);
   } else {
     if (mt == 1) FW_LAUNCH(1, false); else if (mt == 2) FW_LAUNCH(2, false); else FW_LAUNCH(4, false);

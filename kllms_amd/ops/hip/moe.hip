@@ -23,6 +23,13 @@
 // access pattern. Double-buffered BK=64 stages, ONE barrier per stage, with
 // the next stage's global loads issued before the current stage's MFMAs
 // (T14: HBM/L2 latency hides under the matrix work).
+//
+// Both kernels are templates on the weight type. WT = bf16_t is the kernel as
+// it always was. WT = unsigned char takes weight-only fp8 (OCP e4m3) experts
+// with one fp32 scale per (expert, output channel): a staged weight row is
+// loaded at half the bytes, converted to bf16 in registers (exact, fw_cvt4 of
+// common.h) on its way into the SAME swizzled bf16 LDS tile, so the MFMA loop
+// is shared, and the scales multiply the fp32 accumulators in the epilogue.
 
 #include "common.h"
 
@@ -46,13 +53,43 @@ __device__ __forceinline__ int tile_off(int row, int byte_in_row) {
   return row * ROW_B + (byte_in_row ^ ((row & 7) << 4));
 }
 
+// The 32 weights (of one row) that a thread stages per k-stage, in flight
+// between the global load and the LDS store: 4 x 16 B of bf16, or 2 x 16 B of
+// e4m3 widened at the store.
+template <typename WT> struct WStage;
+template <> struct WStage<bf16_t> {
+  bf16x8_vec r[4];
+  __device__ __forceinline__ void load(const bf16_t* p) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = reinterpret_cast<const bf16x8_vec*>(p)[i];
+  }
+  __device__ __forceinline__ bf16x8_vec piece(int i) const { return r[i]; }
+};
+template <> struct WStage<unsigned char> {
+  fw_u32x4 r[2];
+  __device__ __forceinline__ void load(const unsigned char* p) {
+    r[0] = reinterpret_cast<const fw_u32x4*>(p)[0];
+    r[1] = reinterpret_cast<const fw_u32x4*>(p)[1];
+  }
+  __device__ __forceinline__ bf16x8_vec piece(int i) const {   // weights [8i, 8i + 8)
+    uint32_t a, b, c, d;
+    fw_cvt4(r[i >> 1][2 * (i & 1)], a, b);
+    fw_cvt4(r[i >> 1][2 * (i & 1) + 1], c, d);
+    const fw_u32x4 o = {a, b, c, d};
+    return __builtin_bit_cast(bf16x8_vec, o);
+  }
+};
+
 // gate_up: x [T, K] gathered by sorted_ids; w [E, 2*IN, K] fused rows
 // (gate at [0, IN), up at [IN, 2*IN)); act out [S, IN] bf16 in sorted space.
 // pad_offsets [E+1]: sorted-space row range of expert e (multiples of BM).
-extern "C" __global__ void __launch_bounds__(256) moe_gateup_kernel(
+// scale [E, 2*IN] fp32 (fp8 weights only).
+template <typename WT>
+__global__ void __launch_bounds__(256) moe_gateup_kernel(
     bf16_t* __restrict__ act,            // [S, IN]
     const bf16_t* __restrict__ x,        // [T, K]
-    const bf16_t* __restrict__ w,        // [E, 2*IN, K]
+    const WT* __restrict__ w,            // [E, 2*IN, K]
+    const float* __restrict__ scale,     // [E, 2*IN] or nullptr (bf16 weights)
     const int* __restrict__ sorted_ids,  // [S] token index or -1 (pad)
     const int* __restrict__ pad_offsets, // [E+1]
     const bf16_t* __restrict__ zeros,    // [K] zero page for pad rows
@@ -67,7 +104,7 @@ extern "C" __global__ void __launch_bounds__(256) moe_gateup_kernel(
 
   const int m_begin = pad_offsets[e];
   const int m_end = pad_offsets[e + 1];
-  const bf16_t* we = w + (long)e * (2 * (long)IN) * K;
+  const WT* we = w + (long)e * (2 * (long)IN) * K;
 
   // staging assignment: thread t stages 64 B (4 x 16 B) of one row
   const int st_arow = tid >> 1;                 // A: 128 rows x 2 threads
@@ -75,7 +112,7 @@ extern "C" __global__ void __launch_bounds__(256) moe_gateup_kernel(
   const int st_brow = (tid & 127) >> 1;         // B: 64 rows x 2 threads
   const int st_boff = (tid & 1) * 32;
   const bool st_up = tid >= 128;                // low half: gate, high: up
-  const bf16_t* st_bsrc =
+  const WT* st_bsrc =
       we + ((long)((st_up ? IN : 0) + n0 + st_brow)) * K + st_boff;
 
   // [2 buffers][A 16 KB + gate 8 KB + up 8 KB] (offset selection — pointer
@@ -95,15 +132,13 @@ extern "C" __global__ void __launch_bounds__(256) moe_gateup_kernel(
     f32x16 accg[2] = {{}, {}};
     f32x16 accu[2] = {{}, {}};
 
-    bf16x8_vec ra[4], rb[4];
+    bf16x8_vec ra[4];
+    WStage<WT> rb;
     auto ld = [&](int stage) {
       const bf16_t* ap = st_asrc + stage * MOE_BK;
-      const bf16_t* bp = st_bsrc + stage * MOE_BK;
 #pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        ra[p] = reinterpret_cast<const bf16x8_vec*>(ap)[p];
-        rb[p] = reinterpret_cast<const bf16x8_vec*>(bp)[p];
-      }
+      for (int p = 0; p < 4; ++p) ra[p] = reinterpret_cast<const bf16x8_vec*>(ap)[p];
+      rb.load(st_bsrc + stage * MOE_BK);
     };
     auto st = [&](int buf) {
       char* bt = st_up ? u_lds(buf) : g_lds(buf);
@@ -112,7 +147,7 @@ extern "C" __global__ void __launch_bounds__(256) moe_gateup_kernel(
         *reinterpret_cast<bf16x8_vec*>(
             a_lds(buf) + tile_off(st_arow, st_aoff * 2 + p * 16)) = ra[p];
         *reinterpret_cast<bf16x8_vec*>(
-            bt + tile_off(st_brow, st_boff * 2 + p * 16)) = rb[p];
+            bt + tile_off(st_brow, st_boff * 2 + p * 16)) = rb.piece(p);
       }
     };
 
@@ -147,12 +182,21 @@ extern "C" __global__ void __launch_bounds__(256) moe_gateup_kernel(
     // pad slots that the down kernel's own pad handling discards)
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
+      const int n = n0 + ct * 32 + jc;
+      float sg = 1.0f, su = 1.0f;
+      if constexpr (sizeof(WT) == 1) {
+        sg = scale[(long)e * 2 * IN + n];
+        su = scale[(long)e * 2 * IN + IN + n];
+      }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int i = (r & 3) + 8 * (r >> 2) + 4 * half;   // D-row map
         const long out_row = m0 + wv * 32 + i;
-        act[out_row * IN + n0 + ct * 32 + jc] =
-            __float2bfloat16(silu(accg[ct][r]) * accu[ct][r]);
+        if constexpr (sizeof(WT) == 1)
+          act[out_row * IN + n] =
+              __float2bfloat16(silu(accg[ct][r] * sg) * (accu[ct][r] * su));
+        else
+          act[out_row * IN + n] = __float2bfloat16(silu(accg[ct][r]) * accu[ct][r]);
       }
     }
   }
@@ -160,10 +204,13 @@ extern "C" __global__ void __launch_bounds__(256) moe_gateup_kernel(
 
 // down: y[s, :] = act[s] @ Wd[e]^T ; Wd [E, H, IN]; y [S, H] bf16 (sorted
 // space, pad rows garbage-but-confined — rows are independent in MFMA).
-extern "C" __global__ void __launch_bounds__(256) moe_down_kernel(
+// scale [E, H] fp32 (fp8 weights only).
+template <typename WT>
+__global__ void __launch_bounds__(256) moe_down_kernel(
     bf16_t* __restrict__ y,              // [S, H]
     const bf16_t* __restrict__ act,      // [S, IN]
-    const bf16_t* __restrict__ w,        // [E, H, IN]
+    const WT* __restrict__ w,            // [E, H, IN]
+    const float* __restrict__ scale,     // [E, H] or nullptr (bf16 weights)
     const int* __restrict__ pad_offsets, // [E+1]
     int H, int IN, int n_tiles) {
   const int e = blockIdx.x / n_tiles;
@@ -176,14 +223,14 @@ extern "C" __global__ void __launch_bounds__(256) moe_down_kernel(
 
   const int m_begin = pad_offsets[e];
   const int m_end = pad_offsets[e + 1];
-  const bf16_t* we = w + (long)e * (long)H * IN;
+  const WT* we = w + (long)e * (long)H * IN;
 
   const int st_arow = tid >> 1;
   const int st_aoff = (tid & 1) * 32;
   const int st_brow = (tid & 127) >> 1;
   const int st_boff = (tid & 1) * 32;
   const bool st_b = tid < 128;                  // low half stages B
-  const bf16_t* st_bsrc = we + ((long)(n0 + st_brow)) * IN + st_boff;
+  const WT* st_bsrc = we + ((long)(n0 + st_brow)) * IN + st_boff;
 
   __shared__ __attribute__((aligned(16))) char smem[2 * (MOE_BM + MOE_BN) * ROW_B];
   const int BUF_STRIDE = (MOE_BM + MOE_BN) * ROW_B;
@@ -196,16 +243,13 @@ extern "C" __global__ void __launch_bounds__(256) moe_down_kernel(
     const bf16_t* st_asrc = act + (long)(m0 + st_arow) * IN + st_aoff;
 
     f32x16 acc[2] = {{}, {}};
-    bf16x8_vec ra[4], rb[4];
+    bf16x8_vec ra[4];
+    WStage<WT> rb;
     auto ld = [&](int stage) {
       const bf16_t* ap = st_asrc + stage * MOE_BK;
 #pragma unroll
       for (int p = 0; p < 4; ++p) ra[p] = reinterpret_cast<const bf16x8_vec*>(ap)[p];
-      if (st_b) {
-        const bf16_t* bp = st_bsrc + stage * MOE_BK;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) rb[p] = reinterpret_cast<const bf16x8_vec*>(bp)[p];
-      }
+      if (st_b) rb.load(st_bsrc + stage * MOE_BK);
     };
     auto st = [&](int buf) {
 #pragma unroll
@@ -217,7 +261,7 @@ extern "C" __global__ void __launch_bounds__(256) moe_down_kernel(
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
           *reinterpret_cast<bf16x8_vec*>(
-              b_lds(buf) + tile_off(st_brow, st_boff * 2 + p * 16)) = rb[p];
+              b_lds(buf) + tile_off(st_brow, st_boff * 2 + p * 16)) = rb.piece(p);
         }
       }
     };
@@ -248,31 +292,48 @@ extern "C" __global__ void __launch_bounds__(256) moe_down_kernel(
 
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
+      const int n = n0 + ct * 32 + jc;
+      float sc = 1.0f;
+      if constexpr (sizeof(WT) == 1) sc = scale[(long)e * H + n];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int i = (r & 3) + 8 * (r >> 2) + 4 * half;
         const long out_row = m0 + wv * 32 + i;
-        y[out_row * H + n0 + ct * 32 + jc] = __float2bfloat16(acc[ct][r]);
+        if constexpr (sizeof(WT) == 1)
+          y[out_row * H + n] = __float2bfloat16(acc[ct][r] * sc);
+        else
+          y[out_row * H + n] = __float2bfloat16(acc[ct][r]);
       }
     }
   }
 }
 
-extern "C" void launch_moe_gateup(void* act, const void* x, const void* w,
+// scale == nullptr: w is bf16; otherwise w is e4m3 with per-channel scales
+extern "C" void launch_moe_gateup(void* act, const void* x, const void* w, const float* scale,
                                   const int* sorted_ids, const int* pad_offsets,
                                   const void* zeros, int E, int IN, int K,
                                   hipStream_t stream) {
   const int n_tiles = IN / MOE_BN;
-  hipLaunchKernelGGL(moe_gateup_kernel, dim3(E * n_tiles), dim3(256), 0, stream,
-                     (bf16_t*)act, (const bf16_t*)x, (const bf16_t*)w,
-                     sorted_ids, pad_offsets, (const bf16_t*)zeros, IN, K, n_tiles);
+  if (scale == nullptr)
+    hipLaunchKernelGGL(moe_gateup_kernel<bf16_t>, dim3(E * n_tiles), dim3(256), 0, stream,
+                       (bf16_t*)act, (const bf16_t*)x, (const bf16_t*)w, scale,
+                       sorted_ids, pad_offsets, (const bf16_t*)zeros, IN, K, n_tiles);
+  else
+    hipLaunchKernelGGL(moe_gateup_kernel<unsigned char>, dim3(E * n_tiles), dim3(256), 0, stream,
+                       (bf16_t*)act, (const bf16_t*)x, (const unsigned char*)w, scale,
+                       sorted_ids, pad_offsets, (const bf16_t*)zeros, IN, K, n_tiles);
 }
 
-extern "C" void launch_moe_down(void* y, const void* act, const void* w,
+extern "C" void launch_moe_down(void* y, const void* act, const void* w, const float* scale,
                                 const int* pad_offsets, int E, int H, int IN,
                                 hipStream_t stream) {
   const int n_tiles = H / MOE_BN;
-  hipLaunchKernelGGL(moe_down_kernel, dim3(E * n_tiles), dim3(256), 0, stream,
-                     (bf16_t*)y, (const bf16_t*)act, (const bf16_t*)w,
-                     pad_offsets, H, IN, n_tiles);
+  if (scale == nullptr)
+    hipLaunchKernelGGL(moe_down_kernel<bf16_t>, dim3(E * n_tiles), dim3(256), 0, stream,
+                       (bf16_t*)y, (const bf16_t*)act, (const bf16_t*)w, scale,
+                       pad_offsets, H, IN, n_tiles);
+  else
+    hipLaunchKernelGGL(moe_down_kernel<unsigned char>, dim3(E * n_tiles), dim3(256), 0, stream,
+                       (bf16_t*)y, (const bf16_t*)act, (const unsigned char*)w, scale,
+                       pad_offsets, H, IN, n_tiles);
 }

@@ -128,6 +128,16 @@ def linear_fp8w(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor,
     return y.to(x.dtype)
 
 
+def linear_fp8w_batched(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """``out[e] = (x_e @ q[e]^T) * scale[e]`` for e4m3 ``q`` [E, N, K] with fp32
+    ``scale`` [E, N]; ``x`` [M, K] (shared by all experts) or [E, M, K]. fp32
+    accumulation (fp64 for fp64 input); the scale multiplies the accumulated
+    sum, never the weights."""
+    acc = torch.float64 if x.dtype == torch.float64 else torch.float32
+    y = torch.matmul(x.to(acc), q.to(acc).transpose(1, 2)) * scale.to(acc).unsqueeze(1)
+    return y.to(x.dtype)
+
+
 # --- paged KV cache -----------------------------------------------------------
 
 def store_kv(
