@@ -197,6 +197,17 @@ class EngineConfig(BaseModel):
     # groups sharing fewer keys than this are not cascaded (whole 256-key
     # chunks are shared, so 256 is also the floor)
     shared_prefix_min_keys: int = 256
+    # paged prefill attention: chunked prefill (prefill_chunk_tokens) and the
+    # tails of prefix-cache hits attend to K/V that already sits in the paged
+    # cache. By default they run as decode batches with one row per new token
+    # (every row streams its whole context through the per-stream kernel);
+    # with this on they run ONE tiled MFMA kernel that reads each sequence's
+    # cached keys once per 32-row q-tile group (bf16 probabilities into the
+    # MFMA, as in the packed prefill kernel, so the logits differ from the
+    # default path within that kernel's error). Off by default; with it off
+    # nothing changes. The environment variable KLLMS_PAGED_PREFILL_ATTN=1/0,
+    # read once at engine construction, overrides this field.
+    paged_prefill_attention: bool = False
     # cross-request prefix caching: full prompt blocks are published to a
     # digest-keyed cache; later prompts sharing the prefix skip re-prefilling
     # it (LRU + eviction under allocator pressure)

@@ -197,6 +197,14 @@ class LLMEngine:
             raise ValueError(f"KLLMS_SHARED_PREFIX_ATTN must be 0 or 1, got {env_sp!r}")
         self.shared_prefix_attention = (
             config.shared_prefix_attention if not env_sp else env_sp == "1")
+        # paged MFMA prefill attention for chunked prefill and prefix-cache
+        # tails: config field, overridden by KLLMS_PAGED_PREFILL_ATTN=1/0
+        # (read once, here)
+        env_pp = os.environ.get("KLLMS_PAGED_PREFILL_ATTN")
+        if env_pp not in (None, "", "0", "1"):
+            raise ValueError(f"KLLMS_PAGED_PREFILL_ATTN must be 0 or 1, got {env_pp!r}")
+        self.paged_prefill_attention = (
+            config.paged_prefill_attention if not env_pp else env_pp == "1")
         # fp8 (e4m3) layer weights: config field, overridden by
         # KLLMS_WEIGHT_DTYPE=bf16/fp8_e4m3 (read once, here)
         env_wd = os.environ.get("KLLMS_WEIGHT_DTYPE")
@@ -607,17 +615,25 @@ class LLMEngine:
                 ctx_lens.append(p + 1)
                 bt_blocks.append(seq.blocks)
             last_rows.append(len(all_ids) - 1)
-        max_nb = max(len(b) for b in bt_blocks)
-        bt = torch.zeros((len(bt_blocks), max_nb), dtype=torch.int32)
-        for r, blocks in enumerate(bt_blocks):
-            bt[r, : len(blocks)] = torch.tensor(blocks, dtype=torch.int32)
+        if self.paged_prefill_attention:
+            # one tiled kernel over all tails: per-SEQUENCE tables instead of
+            # the per-token [T, nb] table and context lengths
+            attn = dict(extend=ops.build_paged_prefill(
+                [len(ids) - start for ids, start in zip(ids_list, starts)], starts,
+                [seq.blocks for seq in seqs], dev, self.kv.block_size))
+        else:
+            max_nb = max(len(b) for b in bt_blocks)
+            bt = torch.zeros((len(bt_blocks), max_nb), dtype=torch.int32)
+            for r, blocks in enumerate(bt_blocks):
+                bt[r, : len(blocks)] = torch.tensor(blocks, dtype=torch.int32)
+            attn = dict(block_tables=bt.to(dev),
+                        context_lens=torch.tensor(ctx_lens, dtype=torch.int32, device=dev))
         batch = ForwardBatch(
             mode="decode",
             positions=torch.tensor(all_pos, dtype=torch.long, device=dev),
             slot_mapping=torch.tensor(all_slots, dtype=torch.long, device=dev),
             kv_caches=self.kv.layer_caches(),
-            block_tables=bt.to(dev),
-            context_lens=torch.tensor(ctx_lens, dtype=torch.int32, device=dev),
+            **attn,
         )
         hidden = self.model.forward_hidden(torch.tensor(all_ids, dtype=torch.long, device=dev), batch)
         return self.model.compute_logits(hidden[torch.tensor(last_rows, device=dev)])
@@ -694,25 +710,33 @@ class LLMEngine:
         with one row per chunk token (row i: position start+i, context
         start+i+1). Identical math to the packed prefill (RoPE positions and
         causal structure preserved); the LM head runs only on the last token
-        of the final chunk (want_logits=True)."""
+        of the final chunk (want_logits=True). With paged_prefill_attention
+        the rows' attention is ONE call of the tiled paged prefill kernel
+        (ops.attn_prefill_paged) instead of a decode row per token."""
         dev = self.device
         ids = torch.tensor(prompt_ids[start:end], dtype=torch.long, device=dev)
         pos = torch.arange(start, end, dtype=torch.long, device=dev)
         slots_all = self.kv.prefill_slot_mapping(seq)
         slots = torch.tensor(slots_all[start:end], dtype=torch.long, device=dev)
-        nb = len(seq.blocks)
-        bt = (
-            torch.tensor(seq.blocks, dtype=torch.int32, device=dev)
-            .unsqueeze(0).expand(end - start, nb).contiguous()
-        )
-        ctx = torch.arange(start + 1, end + 1, dtype=torch.int32, device=dev)
+        if self.paged_prefill_attention:
+            # the chunk as ONE sequence of the tiled paged kernel (its own
+            # table row, `start` keys already cached), not end-start decode rows
+            attn = dict(extend=ops.build_paged_prefill(
+                [end - start], [start], [seq.blocks], dev, self.kv.block_size))
+        else:
+            nb = len(seq.blocks)
+            bt = (
+                torch.tensor(seq.blocks, dtype=torch.int32, device=dev)
+                .unsqueeze(0).expand(end - start, nb).contiguous()
+            )
+            attn = dict(block_tables=bt,
+                        context_lens=torch.arange(start + 1, end + 1, dtype=torch.int32, device=dev))
         batch = ForwardBatch(
             mode="decode",
             positions=pos,
             slot_mapping=slots,
             kv_caches=self.kv.layer_caches(),
-            block_tables=bt,
-            context_lens=ctx,
+            **attn,
         )
         hidden = self.model.forward_hidden(ids, batch)
         if want_logits:

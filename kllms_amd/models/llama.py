@@ -41,6 +41,11 @@ class ForwardBatch:
     # shared-prefix cascade metadata (ops.SharedPrefix) for the forked streams
     # of a decode batch; None = per-stream decode attention only
     shared: Optional["ops.SharedPrefix"] = None
+    # paged prefill attention (ops.PagedPrefill): the rows are the new tokens
+    # of chunked-prefill / prefix-cache-tail sequences and attention runs the
+    # tiled paged kernel through per-sequence tables (block_tables and
+    # context_lens are then unused); None = decode attention per row
+    extend: Optional["ops.PagedPrefill"] = None
 
 
 class LlamaAttention(nn.Module):
@@ -82,6 +87,9 @@ class LlamaAttention(nn.Module):
 
         if batch.mode == "prefill":
             out = ops.attn_prefill_varlen(q, k, v, batch.cu_seqlens, self.scale)
+        elif batch.extend is not None:
+            out = ops.attn_prefill_paged(
+                q, k_cache, v_cache, batch.extend, self.scale, k_scale, v_scale)
         else:
             out = ops.attn_decode_paged(
                 q, k_cache, v_cache, batch.block_tables, batch.context_lens, self.scale,

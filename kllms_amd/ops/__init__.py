@@ -273,6 +273,106 @@ def attn_decode_paged(
                                        k_scale, v_scale)
 
 
+@dataclass
+class PagedPrefill:
+    """Paged (append / extend) prefill-attention metadata, int32 tensors on the
+    batch's device (``build_paged_prefill``): cu_q [n_seq + 1] — packed row
+    range of each sequence's new tokens; q_start [n_seq] — keys already in the
+    cache; block_tables [n_seq, max_blocks] — ONE table row per sequence;
+    grp_seq [G] and grp_qpos0 [G * 8] — per workgroup its sequence and the
+    first row (relative to cu_q) of each wave's 32-row q-tile, -1 = idle."""
+
+    cu_q: torch.Tensor
+    q_start: torch.Tensor
+    block_tables: torch.Tensor
+    grp_seq: torch.Tensor
+    grp_qpos0: torch.Tensor
+
+    @property
+    def n_seq(self) -> int:
+        return int(self.q_start.shape[0])
+
+    @property
+    def n_groups(self) -> int:
+        return int(self.grp_seq.shape[0])
+
+
+PAGED_PREFILL_WAVES = 8     # q-tile slots per workgroup (attn_prefill_paged.hip)
+PAGED_PREFILL_QBLK = 32
+
+
+def build_paged_prefill(q_lens, q_starts, block_lists, device, block_size: int,
+                        tiles_per_group: Optional[int] = None) -> PagedPrefill:
+    """Build ``PagedPrefill`` from Python lists in one host pass: sequence s
+    appends ``q_lens[s]`` >= 1 tokens after ``q_starts[s]`` >= 0 cached keys and
+    owns the physical blocks ``block_lists[s]`` (of ``block_size`` slots).
+
+    Every 32-row q-tile of every sequence lands in exactly one workgroup slot;
+    a workgroup holds tiles of one sequence only and pads with -1.
+    ``tiles_per_group`` (1..8) is how many tiles share a workgroup's K/V
+    staging; None picks 8 once the batch has 64 tiles and fewer below, so that
+    a short append still spreads over enough workgroups. Raises when a
+    sequence's ``start + len`` does not fit its blocks."""
+    NW, QB = PAGED_PREFILL_WAVES, PAGED_PREFILL_QBLK
+    if not (len(q_lens) == len(q_starts) == len(block_lists)) or len(q_lens) == 0:
+        raise ValueError("build_paged_prefill: need one q_len, q_start and block list per sequence")
+    n_tiles = 0
+    for L, s0, blocks in zip(q_lens, q_starts, block_lists):
+        if L < 1 or s0 < 0:
+            raise ValueError(f"build_paged_prefill: q_len {L} / q_start {s0} out of range")
+        if s0 + L > len(blocks) * block_size:
+            raise ValueError(
+                f"build_paged_prefill: start {s0} + len {L} exceeds the sequence's "
+                f"{len(blocks)} blocks of {block_size}")
+        n_tiles += (L + QB - 1) // QB
+    if tiles_per_group is None:
+        tiles_per_group = min(NW, max(1, n_tiles // 8))
+    if not 1 <= tiles_per_group <= NW:
+        raise ValueError(f"build_paged_prefill: tiles_per_group must be 1..{NW}")
+    max_nb = max(len(b) for b in block_lists)
+    cu = [0]
+    table, grp_seq, grp_qpos0 = [], [], []
+    for s, (L, blocks) in enumerate(zip(q_lens, block_lists)):
+        cu.append(cu[-1] + L)
+        table.append(list(blocks) + [0] * (max_nb - len(blocks)))
+        tiles = list(range(0, L, QB))
+        for g0 in range(0, len(tiles), tiles_per_group):
+            grp = tiles[g0: g0 + tiles_per_group]
+            grp_seq.append(s)
+            grp_qpos0.extend(grp + [-1] * (NW - len(grp)))
+    t = lambda x: torch.tensor(x, dtype=torch.int32, device=device)
+    return PagedPrefill(cu_q=t(cu), q_start=t(list(q_starts)), block_tables=t(table),
+                        grp_seq=t(grp_seq), grp_qpos0=t(grp_qpos0))
+
+
+def attn_prefill_paged(
+    q: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    meta: PagedPrefill,
+    scale: float,
+    k_scale: Optional[torch.Tensor] = None,
+    v_scale: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Causal attention of newly appended tokens over the paged cache: packed
+    row ``cu_q[s] + i`` attends to keys ``0 .. q_start[s] + i`` of sequence s,
+    all read from the cache (``store_kv`` has already written the new ones).
+    On the GPU this is the MFMA kernel of attn_prefill_paged.hip; elsewhere
+    ``torch_ref.attn_prefill_paged``, which is ``attn_decode_paged`` over the
+    per-token rows."""
+    if q.is_cuda and not _force_torch():
+        out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        none = torch.empty(0, dtype=torch.float32, device=q.device)
+        _hip_or_raise().attn_prefill_paged(
+            out, q, k_cache, v_cache, meta.block_tables, meta.cu_q, meta.q_start,
+            meta.grp_seq, meta.grp_qpos0, scale,
+            k_scale if k_scale is not None else none,
+            v_scale if v_scale is not None else none)
+        return out
+    return torch_ref.attn_prefill_paged(q, k_cache, v_cache, meta.block_tables, meta.cu_q,
+                                        meta.q_start, scale, k_scale, v_scale)
+
+
 def sample(
     logits: torch.Tensor,
     temperatures: torch.Tensor,

@@ -1,0 +1,337 @@
+// Paged ("append" / "extend") causal prefill attention for gfx950 — the flash
+// MFMA loop of attn_prefill.hip with its K/V tiles gathered from the paged
+// cache as attn_decode_shared.hip does.
+//
+// Sequence s has q_start[s] keys already in the cache and q_len[s] =
+// cu_q[s+1] - cu_q[s] new tokens packed at rows cu_q[s].. of q/out. Row i of
+// the sequence attends to keys 0 .. q_start[s] + i inclusive, ALL read from
+// k_cache / v_cache through block_tables[s] (one table row per sequence):
+// store_kv has written the new tokens' K/V before attention runs, so there
+// are no k / v arguments. bf16 or e4m3 caches; e4m3 rows are dequantised as
+// bf16(fp8 * row_scale) on the way into LDS.
+//
+// Structure (see attn_prefill.hip for the fragment maps and the LDS layouts):
+//   - an 8-wave workgroup serves up to 8 32-row q-tiles of ONE (sequence,
+//     q-head); the waves share the K/V staging. How many tiles the host packs
+//     per workgroup is its choice (grp_qpos0 = -1 marks an idle wave, which
+//     still helps staging): few tiles per workgroup give a short chunk more
+//     workgroups;
+//   - 64 keys per barrier round; the NEXT round's global loads are issued
+//     before this round's MFMA work and written to LDS after it, so the
+//     gather latency overlaps the compute;
+//   - swapped QK^T, lane-local online softmax with defer-max, P repacked to
+//     bf16 B-fragments, O^T = V^T x P;
+//   - a 32-key sub-tile lying wholly at or below the wave's first row limit
+//     (all prefix keys, and the new keys of earlier tiles) takes no mask; only
+//     sub-tiles overlapping the wave's own diagonal are masked.
+//
+// Robustness: the sequence index, block ids and table indices are clamped,
+// the key loop never passes max_blocks * block_size, rows past q_len are
+// never stored.
+
+#include "common.h"
+
+typedef __bf16 bf16x8_mfma __attribute__((ext_vector_type(8)));
+
+#define PP_QBLK 32
+#define PP_KVBLK 64                // staged keys per barrier round (2 MFMA sub-tiles)
+#define PP_NWAVES 8
+#define PP_K_ROW_BYTES 256         // 128 bf16
+#define PP_VT_ROW 72               // shorts: 64 keys + 8 pad (conflict-free b128 reads)
+
+__device__ __forceinline__ int pp_acc_row(int r, int half) {
+  return (r & 3) + 8 * (r >> 2) + 4 * half;   // C/D row map
+}
+
+// one thread's share of a staged round: a 16-dim sliver of one key's K and V
+template <bool FP8> struct PPRegs;
+template <> struct PPRegs<false> { bf16x8_vec ka, kb, va, vb; };
+template <> struct PPRegs<true> { u8x16_vec k8, v8; float ks, vs; };
+
+template <bool FP8>
+__global__ __launch_bounds__(64 * PP_NWAVES) void attn_prefill_paged_t(
+    bf16_t* __restrict__ out,            // [T, H, 128] contiguous
+    const bf16_t* __restrict__ q,        // [T, H, 128], token stride q_tstride
+    const char* __restrict__ k_cache,    // [NB, KVH, BS, 128], bf16 or fp8
+    const char* __restrict__ v_cache,
+    const float* __restrict__ k_scale,   // [NB, KVH, BS] per-row dequant (FP8 only)
+    const float* __restrict__ v_scale,
+    const int* __restrict__ block_tables,   // [n_seq, max_blocks]
+    const int* __restrict__ cu_q,           // [n_seq + 1]
+    const int* __restrict__ q_start,        // [n_seq]
+    const int* __restrict__ grp_seq,        // [G]
+    const int* __restrict__ grp_qpos0,      // [G * 8], -1 = idle wave
+    float scale, int n_seq, int total_rows, int num_q_heads, int num_kv_heads,
+    int num_blocks, int block_size, int max_blocks, int q_tstride) {
+  const int grp = blockIdx.x;
+  const int h = blockIdx.y;
+  const int g_kv = h / (num_q_heads / num_kv_heads);
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6;
+  const int lane = tid & 63;
+  const int half = lane >> 5;
+  const int col = lane & 31;       // q-row (B/C col) or K/VT row (A row)
+
+  const int seq = min(max(grp_seq[grp], 0), n_seq - 1);
+  const int row0 = cu_q[seq];
+  const int qlen = min(cu_q[seq + 1], total_rows) - row0;
+  if (row0 < 0 || qlen <= 0) return;             // workgroup-uniform
+  const int start = max(q_start[seq], 0);
+  const int qpos0 = grp_qpos0[grp * PP_NWAVES + wave];   // -1: idle wave
+  const bool active = qpos0 >= 0 && qpos0 < qlen;
+  const int my_qpos = active ? qpos0 + col : 0;
+  const int my_limit = start + my_qpos;          // last key this row sees
+  const int kv_cap = (int)min((int64_t)max_blocks * block_size, (int64_t)0x7fffffff);
+
+  __shared__ __attribute__((aligned(16))) char smem[PP_KVBLK * PP_K_ROW_BYTES +
+                                                    128 * PP_VT_ROW * 2];
+  char* k_lds = smem;                                   // [64][256B], XOR-swizzled
+  short* vt_lds = reinterpret_cast<short*>(smem + PP_KVBLK * PP_K_ROW_BYTES);  // [128][72]
+
+  // ---- Q fragments (B-operand): 8 d-slices of 16 --------------------------
+  bf16x8_mfma q_frag[8];
+  {
+    const int qrow_c = row0 + (active ? min(my_qpos, qlen - 1) : 0);
+    const bf16_t* qp = q + (int64_t)qrow_c * q_tstride + h * 128;
+#pragma unroll
+    for (int s = 0; s < 8; ++s)
+      q_frag[s] = *reinterpret_cast<const bf16x8_mfma*>((const short*)qp + s * 16 + half * 8);
+  }
+
+  f32x16 o_acc[4] = {};
+  float m_run = -INFINITY;
+  float l_run = 0.0f;
+
+  // workgroup-wide kv bound: the furthest key any active wave may see
+  int kv_end_grp = 0;
+#pragma unroll
+  for (int w = 0; w < PP_NWAVES; ++w) {
+    const int qp0 = grp_qpos0[grp * PP_NWAVES + w];
+    if (qp0 >= 0 && qp0 < qlen) kv_end_grp = max(kv_end_grp, start + min(qlen, qp0 + PP_QBLK));
+  }
+  kv_end_grp = min(kv_end_grp, kv_cap);
+  const int kv_end_me = active ? min(start + min(qlen, qpos0 + PP_QBLK), kv_cap) : 0;
+
+  const int* bt = block_tables + (int64_t)seq * max_blocks;
+  const int st_key = tid >> 3;               // one key per 8 threads
+  const int st_piece = tid & 7;              // 16-dim sliver of that key
+
+  // global -> registers for the round starting at key kt00
+  auto load_round = [&](int kt00, PPRegs<FP8>& r) {
+    const int gk = kt00 + st_key;
+    if (gk < kv_end_grp) {
+      int blk = bt[min(gk / block_size, max_blocks - 1)];
+      blk = min(max(blk, 0), num_blocks - 1);
+      const int64_t row = ((int64_t)blk * num_kv_heads + g_kv) * block_size + (gk % block_size);
+      if constexpr (FP8) {
+        r.k8 = *reinterpret_cast<const u8x16_vec*>(k_cache + row * 128 + st_piece * 16);
+        r.v8 = *reinterpret_cast<const u8x16_vec*>(v_cache + row * 128 + st_piece * 16);
+        r.ks = k_scale[row];
+        r.vs = v_scale[row];
+      } else {
+        const bf16x8_vec* kp = reinterpret_cast<const bf16x8_vec*>(k_cache + row * 256) + st_piece * 2;
+        const bf16x8_vec* vp = reinterpret_cast<const bf16x8_vec*>(v_cache + row * 256) + st_piece * 2;
+        r.ka = kp[0]; r.kb = kp[1];
+        r.va = vp[0]; r.vb = vp[1];
+      }
+    } else {                                  // past the bound: zero rows
+      if constexpr (FP8) {
+        r.k8 = u8x16_vec{}; r.v8 = u8x16_vec{}; r.ks = 0.0f; r.vs = 0.0f;
+      } else {
+        r.ka = bf16x8_vec{}; r.kb = bf16x8_vec{}; r.va = bf16x8_vec{}; r.vb = bf16x8_vec{};
+      }
+    }
+  };
+
+  // registers -> LDS: K swizzled, V transposed
+  auto store_round = [&](const PPRegs<FP8>& r) {
+    bf16x8_vec ka, kb, va, vb;
+    if constexpr (FP8) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        ka[j] = f32_to_bf16(fp8_to_f32(r.k8[j]) * r.ks);
+        kb[j] = f32_to_bf16(fp8_to_f32(r.k8[8 + j]) * r.ks);
+        va[j] = f32_to_bf16(fp8_to_f32(r.v8[j]) * r.vs);
+        vb[j] = f32_to_bf16(fp8_to_f32(r.v8[8 + j]) * r.vs);
+      }
+    } else {
+      ka = r.ka; kb = r.kb; va = r.va; vb = r.vb;
+    }
+    const int swz = (st_key & 15) << 4;
+    *reinterpret_cast<bf16x8_vec*>(k_lds + st_key * PP_K_ROW_BYTES + ((st_piece * 32) ^ swz)) = ka;
+    *reinterpret_cast<bf16x8_vec*>(k_lds + st_key * PP_K_ROW_BYTES + ((st_piece * 32 + 16) ^ swz)) = kb;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      vt_lds[(st_piece * 16 + j) * PP_VT_ROW + st_key] = va[j];
+      vt_lds[(st_piece * 16 + 8 + j) * PP_VT_ROW + st_key] = vb[j];
+    }
+  };
+
+  PPRegs<FP8> regs;
+  load_round(0, regs);
+
+  for (int kt00 = 0; kt00 < kv_end_grp; kt00 += PP_KVBLK) {
+    const int nkeys_blk = min(PP_KVBLK, kv_end_grp - kt00);
+    store_round(regs);
+    __syncthreads();
+    // next round's gather flies under this round's MFMA work
+    if (kt00 + PP_KVBLK < kv_end_grp) load_round(kt00 + PP_KVBLK, regs);
+
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub) {
+    const int kt0 = kt00 + sub * 32;
+    const int nkeys = min(32, nkeys_blk - sub * 32);
+    if (active && kt0 < kv_end_me && nkeys > 0) {
+      // ---- QK^T: S[key][qrow] over 8 d-slices -----------------------------
+      f32x16 s_acc = {};
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const int byte_off = (s * 2 + half) * 16;
+        const int krow = col + sub * 32;
+        bf16x8_mfma a_frag = *reinterpret_cast<const bf16x8_mfma*>(
+            k_lds + krow * PP_K_ROW_BYTES + (byte_off ^ ((krow & 15) << 4)));
+        s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_frag, q_frag[s], s_acc, 0, 0, 0);
+      }
+
+      // ---- scale (+ causal mask on the diagonal sub-tiles only) ------------
+      // every key of a sub-tile ending at or before the wave's FIRST row limit
+      // is visible to all 32 rows (and is below kv_end_grp, so it is staged)
+      float sv[16];
+      if (nkeys == 32 && kt0 + 31 <= start + qpos0) {        // wave-uniform
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sv[r] = s_acc[r] * scale;
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int kr = pp_acc_row(r, half);
+          const bool ok = (kt0 + kr <= my_limit) && (kr < nkeys);
+          sv[r] = ok ? s_acc[r] * scale : -INFINITY;
+        }
+      }
+
+      // ---- online softmax (row = lane-local) -------------------------------
+      float tmax = sv[0];
+#pragma unroll
+      for (int r = 1; r < 16; ++r) tmax = fmaxf(tmax, sv[r]);
+      {
+        auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(tmax), __float_as_uint(tmax), false, false);
+        tmax = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
+      }
+      // defer-max: keep the old running max while the tile max grew < THR (P
+      // then bounded by e^THR); decided BEFORE this tile's P is exponentiated
+      const float DEFER_THR = 8.0f;
+      float m_new, alpha;
+      if (tmax <= m_run + DEFER_THR) {       // first tile: m_run=-inf fails this
+        m_new = m_run;
+        alpha = 1.0f;
+      } else {
+        m_new = fmaxf(m_run, tmax);
+        alpha = (m_run == -INFINITY) ? 0.0f : __expf(m_run - m_new);
+      }
+      m_run = m_new;
+      if (__builtin_amdgcn_ballot_w64(alpha != 1.0f)) {
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) o_acc[dt][r] *= alpha;
+      }
+
+      float p[16];
+      float psum = 0.0f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        p[r] = (sv[r] == -INFINITY) ? 0.0f : __expf(sv[r] - m_new);
+        psum += p[r];
+      }
+      l_run = l_run * alpha + psum;
+
+      // ---- repack P -> bf16 B-fragments (half swaps) -----------------------
+      uint32_t packs[8];
+#pragma unroll
+      for (int pr = 0; pr < 8; ++pr) {
+        const short lo = f32_to_bf16(p[2 * pr]);
+        const short hi = f32_to_bf16(p[2 * pr + 1]);
+        packs[pr] = ((uint32_t)(uint16_t)hi << 16) | (uint16_t)lo;
+      }
+      uint32_t bfrag[2][4];
+#pragma unroll
+      for (int kt = 0; kt < 2; ++kt) {
+        auto r0 = __builtin_amdgcn_permlane32_swap(packs[4 * kt + 0], packs[4 * kt + 2], false, false);
+        auto r1 = __builtin_amdgcn_permlane32_swap(packs[4 * kt + 1], packs[4 * kt + 3], false, false);
+        bfrag[kt][0] = r0[0];
+        bfrag[kt][1] = r1[0];
+        bfrag[kt][2] = r0[1];
+        bfrag[kt][3] = r1[1];
+      }
+
+      // ---- PV: O^T += V^T x P ----------------------------------------------
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        const int d_row = dt * 32 + col;
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt) {
+          bf16x8_mfma vfrag = *reinterpret_cast<const bf16x8_mfma*>(
+              vt_lds + d_row * PP_VT_ROW + sub * 32 + kt * 16 + half * 8);
+          bf16x8_mfma pfrag;
+          {
+            uint32_t* pf = reinterpret_cast<uint32_t*>(&pfrag);
+#pragma unroll
+            for (int w = 0; w < 4; ++w) pf[w] = bfrag[kt][w];
+          }
+          o_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfrag, pfrag, o_acc[dt], 0, 0, 0);
+        }
+      }
+    }
+    }  // sub
+    __syncthreads();   // the staging buffers are rewritten next round
+  }
+
+  // ---- epilogue: merge half-sums, normalize, write O ----------------------
+  {
+    auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
+    l_run = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
+  }
+  if (active && my_qpos < qlen) {
+    const float inv_l = (l_run > 0.0f) ? 1.0f / l_run : 0.0f;
+    bf16_t* op = out + (((int64_t)(row0 + my_qpos)) * num_q_heads + h) * 128;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+#pragma unroll
+      for (int g2 = 0; g2 < 4; ++g2) {   // regs 4*g2..+3 = d consecutive
+        const int d0 = dt * 32 + 8 * g2 + 4 * half;
+        uint64_t word = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float val = o_acc[dt][4 * g2 + j] * inv_l;
+          word |= ((uint64_t)(uint16_t)f32_to_bf16(val)) << (16 * j);
+        }
+        *reinterpret_cast<uint64_t*>((short*)op + d0) = word;
+      }
+    }
+  }
+}
+
+// host-side launcher; an empty grid is the caller's to skip
+extern "C" void launch_attn_prefill_paged(
+    bf16_t* out, const bf16_t* q, const void* k_cache, const void* v_cache,
+    const float* k_scale, const float* v_scale, const int* block_tables,
+    const int* cu_q, const int* q_start, const int* grp_seq, const int* grp_qpos0,
+    float scale, int n_seq, int total_rows, int num_q_heads, int num_kv_heads,
+    int num_blocks, int block_size, int max_blocks, int q_tstride, int n_groups,
+    int cache_fp8, hipStream_t stream) {
+  if (n_groups <= 0 || n_seq <= 0 || total_rows <= 0) return;
+  const dim3 grid(n_groups, num_q_heads);
+  if (cache_fp8) {
+    hipLaunchKernelGGL((attn_prefill_paged_t<true>), grid, dim3(64 * PP_NWAVES), 0, stream,
+                       out, q, (const char*)k_cache, (const char*)v_cache, k_scale, v_scale,
+                       block_tables, cu_q, q_start, grp_seq, grp_qpos0, scale, n_seq,
+                       total_rows, num_q_heads, num_kv_heads, num_blocks, block_size,
+                       max_blocks, q_tstride);
+  } else {
+    hipLaunchKernelGGL((attn_prefill_paged_t<false>), grid, dim3(64 * PP_NWAVES), 0, stream,
+                       out, q, (const char*)k_cache, (const char*)v_cache, k_scale, v_scale,
+                       block_tables, cu_q, q_start, grp_seq, grp_qpos0, scale, n_seq,
+                       total_rows, num_q_heads, num_kv_heads, num_blocks, block_size,
+                       max_blocks, q_tstride);
+  }
+}

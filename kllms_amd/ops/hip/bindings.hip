@@ -15,6 +15,7 @@ extern "C" __global__ void store_kv_kernel(const bf16_t*, const bf16_t*, bf16_t*
 extern "C" __global__ void store_kv_fp8_kernel(const bf16_t*, const bf16_t*, unsigned char*, unsigned char*, float*, float*, const int64_t*, int, int, int, int, int);
 extern "C" void launch_attn_decode_partial(float*, const bf16_t*, const void*, const void*, const float*, const float*, const int*, const int*, const int*, float, int, int, int, int, int, int, int, int, int, hipStream_t);
 extern "C" void launch_attn_decode_shared(float*, const bf16_t*, const void*, const void*, const float*, const float*, const int*, const int*, const int*, const int*, float, int, int, int, int, int, int, int, int, int, int, hipStream_t);
+extern "C" void launch_attn_prefill_paged(bf16_t*, const bf16_t*, const void*, const void*, const float*, const float*, const int*, const int*, const int*, const int*, const int*, float, int, int, int, int, int, int, int, int, int, int, hipStream_t);
 extern "C" __global__ void attn_decode_reduce_kernel(bf16_t*, const float*, const int*, int, int, int, int);
 extern "C" __global__ void attn_prefill_kernel(bf16_t*, const bf16_t*, const bf16_t*, const bf16_t*, const int*, const int*, const int*, float, int, int, int, int);  // grouped: [G], [G], [G*8]
 extern "C" __global__ void sample_kernel(int64_t*, float*, const float*, const float*, const float*, const int*, const int64_t*, const int64_t*, const uint32_t*, int, float*);
@@ -214,6 +215,61 @@ void attn_prefill(torch::Tensor out, torch::Tensor q, torch::Tensor k, torch::Te
                      grp_seq_start.data_ptr<int>(), grp_seqlen.data_ptr<int>(),
                      grp_qpos0.data_ptr<int>(), (float)scale, H, KVH,
                      (int)q.stride(0), (int)k.stride(0));
+}
+
+// Paged (append / extend) prefill attention: new tokens packed at rows
+// cu_q[s]..cu_q[s+1] attend causally to the q_start[s] keys already cached
+// plus themselves, all read through block_tables[s] (one row per sequence).
+// grp_seq [G] / grp_qpos0 [G*8] are the per-workgroup q-tiles of
+// ops.build_paged_prefill, which also checks q_start + q_len against the
+// table width on the host.
+void attn_prefill_paged(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
+                        torch::Tensor v_cache, torch::Tensor block_tables, torch::Tensor cu_q,
+                        torch::Tensor q_start, torch::Tensor grp_seq, torch::Tensor grp_qpos0,
+                        double scale, torch::Tensor k_scale, torch::Tensor v_scale) {
+  CHECK_BF16_CONTIG(out); CHECK_BF16_ROWS(q); CHECK_KV_CACHE(k_cache); CHECK_KV_CACHE(v_cache);
+  TORCH_CHECK(k_cache.dim() == 4 && v_cache.sizes() == k_cache.sizes() &&
+                  v_cache.scalar_type() == k_cache.scalar_type(),
+              "attn_prefill_paged: k_cache/v_cache must be [NB, KVH, BS, D] of one dtype");
+  const int T = q.size(0), H = q.size(1), D = q.size(2);
+  const int KVH = k_cache.size(1), BS = k_cache.size(2);
+  TORCH_CHECK(D == 128 && k_cache.size(3) == 128, "attn_prefill_paged: head_dim must be 128");
+  TORCH_CHECK(KVH > 0 && H % KVH == 0, "attn_prefill_paged: H must be a multiple of KVH");
+  TORCH_CHECK(out.dim() == 3 && out.sizes() == q.sizes(), "attn_prefill_paged: out must be [T, H, D]");
+  TORCH_CHECK(q.stride(0) >= (int64_t)H * D && q.stride(0) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "attn_prefill_paged: q token stride must cover H*D and keep rows 16-byte aligned");
+  auto ok = [](const torch::Tensor& t) {
+    return t.is_cuda() && t.is_contiguous() && t.scalar_type() == at::kInt;
+  };
+  TORCH_CHECK(ok(block_tables) && ok(cu_q) && ok(q_start) && ok(grp_seq) && ok(grp_qpos0),
+              "attn_prefill_paged: metadata must be contiguous int32 on GPU");
+  const int n_seq = q_start.numel();
+  TORCH_CHECK(n_seq >= 1 && cu_q.numel() == n_seq + 1, "cu_q must be [n_seq + 1]");
+  TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(0) == n_seq && block_tables.size(1) >= 1,
+              "block_tables must be [n_seq, max_blocks]");
+  const int n_groups = grp_seq.numel();
+  TORCH_CHECK(grp_qpos0.numel() == (int64_t)n_groups * 8, "grp_qpos0 must be [G*8]");
+  const int cache_fp8 = k_cache.scalar_type() == at::kFloat8_e4m3fn ? 1 : 0;
+  if (cache_fp8) {
+    TORCH_CHECK(k_scale.is_cuda() && v_scale.is_cuda() &&
+                    k_scale.numel() == k_cache.size(0) * KVH * BS && k_scale.is_contiguous() &&
+                    v_scale.is_contiguous() && k_scale.scalar_type() == at::kFloat &&
+                    v_scale.scalar_type() == at::kFloat && v_scale.numel() == k_scale.numel(),
+                "fp8 attn_prefill_paged requires [NB, KVH, BS] fp32 k_scale/v_scale");
+  } else {
+    TORCH_CHECK(k_scale.numel() == 0 && v_scale.numel() == 0,
+                "attn_prefill_paged: k_scale/v_scale go with fp8 caches only");
+  }
+  if (T == 0 || n_groups == 0) return;
+  launch_attn_prefill_paged(
+      bf(out), cbf(q), k_cache.data_ptr(), v_cache.data_ptr(),
+      cache_fp8 ? k_scale.data_ptr<float>() : nullptr,
+      cache_fp8 ? v_scale.data_ptr<float>() : nullptr,
+      block_tables.data_ptr<int>(), cu_q.data_ptr<int>(), q_start.data_ptr<int>(),
+      grp_seq.data_ptr<int>(), grp_qpos0.data_ptr<int>(), (float)scale, n_seq, T, H, KVH,
+      (int)k_cache.size(0), BS, (int)block_tables.size(1), (int)q.stride(0), n_groups,
+      cache_fp8, cur_stream());
 }
 
 void sample(torch::Tensor tokens, torch::Tensor logprobs, torch::Tensor logits,
@@ -558,6 +614,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_paged", &attn_decode_paged);
   m.def("attn_decode_paged_shared", &attn_decode_paged_shared);
   m.def("attn_prefill", &attn_prefill);
+  m.def("attn_prefill_paged", &attn_prefill_paged);
   m.def("sample", &sample);
   m.def("sample_fsm", &sample_fsm);
   m.def("mfma_selftest", &mfma_selftest);

@@ -241,6 +241,25 @@ def attn_decode_paged(
     return out
 
 
+def attn_prefill_paged(q, k_cache, v_cache, block_tables, cu_q, q_start, scale,
+                       k_scale=None, v_scale=None) -> torch.Tensor:
+    """Paged (append) prefill attention, DEFINED as ``attn_decode_paged`` over
+    the expanded per-token rows: packed row ``cu_q[s] + i`` gets sequence s's
+    table row and ``context_lens = q_start[s] + i + 1``. block_tables is
+    [n_seq, max_blocks] (one row per sequence)."""
+    cu = [int(c) for c in cu_q]
+    starts = [int(c) for c in q_start]
+    rows, lens = [], []
+    for s in range(len(starts)):
+        n = cu[s + 1] - cu[s]
+        rows.extend([s] * n)
+        lens.extend(range(starts[s] + 1, starts[s] + n + 1))
+    dev = block_tables.device
+    bt = block_tables[torch.tensor(rows, dtype=torch.long, device=dev)]
+    ctx = torch.tensor(lens, dtype=torch.int32, device=dev)
+    return attn_decode_paged(q, k_cache, v_cache, bt, ctx, scale, k_scale, v_scale)
+
+
 def _paged_partial(qb, k_cache, v_cache, blocks_row, k0, k1, scale, k_scale, v_scale):
     """Unnormalised softmax partial of one row's heads over keys [k0, k1) read
     through ``blocks_row``: (m [H], l [H], o [H, D]) in fp32."""

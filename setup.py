@@ -23,6 +23,7 @@ SOURCES = [
         "attn_decode.hip",
         "attn_decode_shared.hip",
         "attn_prefill.hip",
+        "attn_prefill_paged.hip",
         "sampling.hip",
         "mfma_selftest.hip",
         "allreduce.hip",
