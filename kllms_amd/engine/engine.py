@@ -670,6 +670,10 @@ class LLMEngine:
         refs) and sample the first token of every stream from that request's
         prefill logits row."""
         new_streams: List[_Stream] = []
+        # one fork for the whole admitted batch: all refcounts and tail-block
+        # allocations first, then every tail copy in a single launch
+        forked = self.kv.fork_batch(
+            [(parent_seqs[ri], max(1, req.n)) for ri, req in enumerate(requests)])
         for ri, req in enumerate(requests):
             # unseeded requests draw from a per-engine monotonic counter, NOT
             # the batch-local index: sampled output must not depend on which
@@ -681,15 +685,26 @@ class LLMEngine:
             fork_id = self._fork_counter
             self._fork_counter += 1
             for si in range(max(1, req.n)):
-                seq = self.kv.fork(parent_seqs[ri])
-                cstate = req.constraint.init_state() if req.constraint is not None else None
-                st = _Stream(ri, si, seq, req.sampling, seed=base_seed + 7919 * si,
-                             constraint=req.constraint, constraint_state=cstate,
-                             fork_id=fork_id)
+                seq = forked[ri][si]
+                try:
+                    cstate = req.constraint.init_state() if req.constraint is not None else None
+                    st = _Stream(ri, si, seq, req.sampling, seed=base_seed + 7919 * si,
+                                 constraint=req.constraint, constraint_state=cstate,
+                                 fork_id=fork_id)
+                except Exception:
+                    # children not yet owned by a stream would leak their blocks
+                    for children in forked:
+                        for child in children:
+                            if child.blocks and all(child is not s.seq for s in new_streams):
+                                self.kv.free_sequence(child)
+                    raise
                 st.deadline = req.deadline if self.ctx.world_size == 1 else None
                 streams.append(st)
                 new_streams.append(st)
-            self.kv.free_sequence(parent_seqs[ri])  # streams hold their own refs
+        # the copies are already enqueued, so stream order protects the tail
+        # blocks the parents give back here; streams hold their own refs
+        for seq in parent_seqs[:len(requests)]:
+            self.kv.free_sequence(seq)
 
         rep_logits = torch.cat([
             prefill_logits[ri].unsqueeze(0).expand(max(1, requests[ri].n), -1)

@@ -20,6 +20,8 @@ from typing import Callable, List, Optional, Tuple
 
 import torch
 
+from .. import ops
+
 
 class BlockAllocator:
     def __init__(self, num_blocks: int):
@@ -126,29 +128,69 @@ class PagedKVCache:
         """Share the parent's blocks by refcount. The block the child will
         write into next (a partially-filled tail block) is copied EAGERLY so
         the decode hot loop never needs copy-on-write bookkeeping."""
-        child = SequenceKV(blocks=[], num_tokens=parent.num_tokens)
-        tail = parent.num_tokens % self.block_size
+        return self.fork_batch([(parent, 1)])[0][0]
+
+    def fork_batch(self, parents_and_counts) -> List[List[SequenceKV]]:
+        """``fork`` for a whole admitted batch: ``parents_and_counts`` is a list
+        of ``(parent, n_children)``; returns the children per parent, in order.
+
+        Refcounts and tail-block allocations are done for every child first;
+        then the (src, dst) pair list is uploaded once and all tail copies run
+        as ONE launch (two for an fp8 cache: payload, scales), immediately and
+        on the current stream -- a caller that frees the parents afterwards is
+        protected by stream order. A source may feed many children; a block is
+        never both a source and a destination of one call (sources are live
+        parent blocks, destinations come fresh from the free list). When the
+        allocator runs dry every block taken so far is released and nothing
+        is copied."""
+        out: List[List[SequenceKV]] = []
+        src: List[int] = []
+        dst: List[int] = []
         try:
-            for i, b in enumerate(parent.blocks):
-                if i == len(parent.blocks) - 1 and tail != 0:
-                    child.blocks.append(self._copy_block(b))
-                else:
-                    self.allocator.incref(b)
-                    child.blocks.append(b)
+            for parent, count in parents_and_counts:
+                tail = parent.num_tokens % self.block_size
+                last = len(parent.blocks) - 1
+                children: List[SequenceKV] = []
+                out.append(children)
+                for _ in range(count):
+                    child = SequenceKV(blocks=[], num_tokens=parent.num_tokens)
+                    children.append(child)
+                    for i, b in enumerate(parent.blocks):
+                        if i == last and tail != 0:
+                            child.blocks.append(self.allocator.alloc())
+                            src.append(b)
+                            dst.append(child.blocks[-1])
+                        else:
+                            self.allocator.incref(b)
+                            child.blocks.append(b)
         except Exception:
-            for b in child.blocks:
-                self.allocator.free(b)
-            child.blocks = []
+            for children in out:
+                for child in children:
+                    for b in child.blocks:
+                        self.allocator.free(b)
+                    child.blocks = []
             raise
-        return child
+        self._copy_blocks(src, dst)
+        return out
+
+    def _copy_blocks(self, src: List[int], dst: List[int]) -> None:
+        """Copy blocks src[i] -> dst[i] in every layer of K and V (and of the
+        fp8 scale arrays), one launch per pair of arrays."""
+        if not src:
+            return
+        assert len(src) == len(dst)
+        assert all(0 <= b < self.num_blocks for b in src) and \
+            all(0 <= b < self.num_blocks for b in dst), "block id out of range"
+        assert len(set(dst)) == len(dst), "a block is the destination of two copies"
+        assert set(src).isdisjoint(dst), "a block is both a source and a destination"
+        pairs = torch.tensor([src, dst], dtype=torch.int32).to(self.k_all.device)
+        ops.copy_kv_blocks(self.k_all, self.v_all, pairs[0], pairs[1])
+        if self.fp8:
+            ops.copy_kv_blocks(self.k_scale_all, self.v_scale_all, pairs[0], pairs[1])
 
     def _copy_block(self, src: int) -> int:
         dst = self.allocator.alloc()
-        self.k_all[:, dst].copy_(self.k_all[:, src])
-        self.v_all[:, dst].copy_(self.v_all[:, src])
-        if self.fp8:
-            self.k_scale_all[:, dst].copy_(self.k_scale_all[:, src])
-            self.v_scale_all[:, dst].copy_(self.v_scale_all[:, src])
+        self._copy_blocks([src], [dst])
         return dst
 
     def append_slot(self, seq: SequenceKV) -> int:

@@ -80,10 +80,11 @@ class LlamaAttention(nn.Module):
         q = q.view(T, self.num_heads, self.head_dim)
         k = k.view(T, self.num_kv_heads, self.head_dim)
         v = v.view(T, self.num_kv_heads, self.head_dim)
-        ops.rope_inplace(q, k, batch.positions, cos_sin)
-
+        # RoPE on q/k and the scatter of the rotated k and of v into the paged
+        # cache: one launch, the bits of rope_inplace followed by store_kv
         k_cache, v_cache, k_scale, v_scale = batch.kv_caches[self.layer_idx]
-        ops.store_kv(k, v, k_cache, v_cache, batch.slot_mapping, k_scale, v_scale)
+        ops.rope_store_kv(q, k, v, batch.positions, cos_sin, k_cache, v_cache,
+                          batch.slot_mapping, k_scale, v_scale)
 
         if batch.mode == "prefill":
             out = ops.attn_prefill_varlen(q, k, v, batch.cu_seqlens, self.scale)

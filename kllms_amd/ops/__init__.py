@@ -188,6 +188,49 @@ def store_kv(
     torch_ref.store_kv(k, v, k_cache, v_cache, slot_mapping, k_scale, v_scale)
 
 
+def rope_store_kv(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    positions: torch.Tensor,
+    cos_sin: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    slot_mapping: torch.Tensor,
+    k_scale: Optional[torch.Tensor] = None,
+    v_scale: Optional[torch.Tensor] = None,
+) -> None:
+    """``rope_inplace(q, k, ...)`` followed by ``store_kv(k, v, ...)`` as ONE
+    kernel on the GPU: q and k are rotated in place, the rotated k and the
+    untouched v go to the paged caches at ``slot_mapping``. q, k, both caches
+    and (fp8) both scale arrays end up with the bits of the two separate ops."""
+    if q.is_cuda and not _force_torch():
+        none = torch.empty(0, dtype=torch.float32, device=q.device)
+        _hip_or_raise().rope_store_kv(
+            q, k, v, positions, cos_sin, k_cache, v_cache, slot_mapping,
+            k_scale if k_scale is not None else none,
+            v_scale if v_scale is not None else none)
+        return
+    torch_ref.rope_inplace(q, k, positions, cos_sin)
+    torch_ref.store_kv(k, v, k_cache, v_cache, slot_mapping, k_scale, v_scale)
+
+
+def copy_kv_blocks(a_all: torch.Tensor, b_all: torch.Tensor,
+                   src: torch.Tensor, dst: torch.Tensor) -> None:
+    """Copy blocks ``src[i] -> dst[i]`` (int32 [n], on the arrays' device) of
+    the two ``[L, NB, ...]`` arrays ``a_all`` and ``b_all`` in every layer: one
+    HIP launch on the GPU, torch indexing on the CPU. A source may repeat; the
+    caller guarantees that no block is both a source and a destination."""
+    if src.numel() == 0:
+        return
+    if a_all.is_cuda and not _force_torch():
+        _hip_or_raise().copy_kv_blocks(a_all, b_all, src, dst)
+        return
+    s, d = src.long(), dst.long()
+    a_all[:, d] = a_all[:, s]
+    b_all[:, d] = b_all[:, s]
+
+
 def _prefill_tiles(cu_seqlens: torch.Tensor, device) -> tuple:
     """Grouped q-tile metadata for the MFMA prefill kernel: 32-row q-tiles of
     each sequence packed 8 per workgroup (the 8 waves share the K/V LDS

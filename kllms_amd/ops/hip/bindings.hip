@@ -13,6 +13,9 @@ extern "C" __global__ void silu_mul_kernel(bf16_t*, const bf16_t*, const bf16_t*
 extern "C" __global__ void rope_kernel(bf16_t*, bf16_t*, const int64_t*, const float*, int, int, int, int, int);
 extern "C" __global__ void store_kv_kernel(const bf16_t*, const bf16_t*, bf16_t*, bf16_t*, const int64_t*, int, int, int, int, int);
 extern "C" __global__ void store_kv_fp8_kernel(const bf16_t*, const bf16_t*, unsigned char*, unsigned char*, float*, float*, const int64_t*, int, int, int, int, int);
+extern "C" __global__ void rope_store_kv_kernel(bf16_t*, bf16_t*, const bf16_t*, bf16_t*, bf16_t*, const int64_t*, const float*, const int64_t*, int, int, int, int, int, int, int);
+extern "C" __global__ void rope_store_kv_fp8_kernel(bf16_t*, bf16_t*, const bf16_t*, unsigned char*, unsigned char*, float*, float*, const int64_t*, const float*, const int64_t*, int, int, int, int, int, int, int);
+extern "C" void launch_copy_kv_blocks(void*, void*, const int*, const int*, int, int, int64_t, int64_t, int, hipStream_t);
 extern "C" void launch_attn_decode_partial(float*, const bf16_t*, const void*, const void*, const float*, const float*, const int*, const int*, const int*, float, int, int, int, int, int, int, int, int, int, hipStream_t);
 extern "C" void launch_attn_decode_shared(float*, const bf16_t*, const void*, const void*, const float*, const float*, const int*, const int*, const int*, const int*, float, int, int, int, int, int, int, int, int, int, int, hipStream_t);
 extern "C" void launch_attn_prefill_paged(bf16_t*, const bf16_t*, const void*, const void*, const float*, const float*, const int*, const int*, const int*, const int*, const int*, float, int, int, int, int, int, int, int, int, int, int, hipStream_t);
@@ -110,6 +113,84 @@ void store_kv(torch::Tensor k, torch::Tensor v, torch::Tensor k_cache, torch::Te
                        cbf(k), cbf(v), bf(k_cache), bf(v_cache),
                        slot_mapping.data_ptr<int64_t>(), T, KVH, D, BS, (int)k.stride(0));
   }
+}
+
+// rope_inplace + store_kv in one launch (elementwise.hip): q/k rotated in
+// place, the rotated k and the untouched v scattered to the paged caches at
+// slot_mapping. Same views and the same bits as the two separate ops.
+void rope_store_kv(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor positions,
+                   torch::Tensor cos_sin, torch::Tensor k_cache, torch::Tensor v_cache,
+                   torch::Tensor slot_mapping, torch::Tensor k_scale, torch::Tensor v_scale) {
+  CHECK_BF16_ROWS(q); CHECK_BF16_ROWS(k); CHECK_BF16_ROWS(v);
+  CHECK_KV_CACHE(k_cache); CHECK_KV_CACHE(v_cache);
+  TORCH_CHECK(positions.is_cuda() && positions.scalar_type() == at::kLong && positions.is_contiguous() &&
+              cos_sin.is_cuda() && cos_sin.scalar_type() == at::kFloat && cos_sin.is_contiguous(),
+              "rope_store_kv: positions must be int64 and cos_sin fp32, contiguous on GPU");
+  TORCH_CHECK(slot_mapping.is_cuda() && slot_mapping.scalar_type() == at::kLong &&
+              slot_mapping.is_contiguous(), "rope_store_kv: slot_mapping must be contiguous int64 on GPU");
+  const int T = q.size(0), H = q.size(1), D = q.size(2), KVH = k.size(1);
+  TORCH_CHECK(k.size(0) == T && v.size(0) == T && k.size(2) == D && v.size(2) == D &&
+              v.size(1) == KVH, "rope_store_kv: q/k/v disagree on T, KVH or D");
+  TORCH_CHECK(positions.numel() == T && slot_mapping.numel() == T,
+              "rope_store_kv: positions and slot_mapping must be [T]");
+  TORCH_CHECK(k_cache.dim() == 4 && v_cache.sizes() == k_cache.sizes() &&
+              v_cache.scalar_type() == k_cache.scalar_type() && k_cache.size(1) == KVH &&
+              k_cache.size(3) == D && cos_sin.size(-1) == D,
+              "rope_store_kv: caches must be [NB, KVH, BS, D] of one dtype, cos_sin [max_pos, D]");
+  TORCH_CHECK(D % 8 == 0 && v.stride(0) % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(v.data_ptr()) % 16 == 0,
+              "rope_store_kv: head_dim must be a multiple of 8 and v rows 16-byte aligned");
+  if (T == 0) return;
+  const int BS = k_cache.size(2);
+  const dim3 grid(T, (H + KVH + 3) / 4);
+  if (k_cache.scalar_type() == at::kFloat8_e4m3fn) {
+    TORCH_CHECK(k_scale.is_cuda() && v_scale.is_cuda() &&
+                    k_scale.numel() == k_cache.size(0) * KVH * BS && k_scale.is_contiguous() &&
+                    v_scale.is_contiguous() && k_scale.scalar_type() == at::kFloat &&
+                    v_scale.scalar_type() == at::kFloat && v_scale.numel() == k_scale.numel(),
+                "fp8 rope_store_kv requires [NB, KVH, BS] fp32 k_scale/v_scale");
+    hipLaunchKernelGGL(rope_store_kv_fp8_kernel, grid, dim3(256), 0, cur_stream(),
+                       bf(q), bf(k), cbf(v),
+                       reinterpret_cast<unsigned char*>(k_cache.data_ptr()),
+                       reinterpret_cast<unsigned char*>(v_cache.data_ptr()),
+                       k_scale.data_ptr<float>(), v_scale.data_ptr<float>(),
+                       positions.data_ptr<int64_t>(), cos_sin.data_ptr<float>(),
+                       slot_mapping.data_ptr<int64_t>(), H, KVH, D, BS,
+                       (int)q.stride(0), (int)k.stride(0), (int)v.stride(0));
+  } else {
+    hipLaunchKernelGGL(rope_store_kv_kernel, grid, dim3(256), 0, cur_stream(),
+                       bf(q), bf(k), cbf(v), bf(k_cache), bf(v_cache),
+                       positions.data_ptr<int64_t>(), cos_sin.data_ptr<float>(),
+                       slot_mapping.data_ptr<int64_t>(), H, KVH, D, BS,
+                       (int)q.stride(0), (int)k.stride(0), (int)v.stride(0));
+  }
+}
+
+// Copy blocks src[i] -> dst[i] of the two [L, NB, ...] arrays `a` and `b` (K
+// and V, or the two fp8 scale arrays) for every layer in one launch
+// (kv_copy.hip). src/dst: int32 [n] on the GPU, validated by the caller
+// (in range, no block both a source and a destination).
+void copy_kv_blocks(torch::Tensor a, torch::Tensor b, torch::Tensor src, torch::Tensor dst) {
+  TORCH_CHECK(a.is_cuda() && b.is_cuda() && a.is_contiguous() && b.is_contiguous() &&
+              a.dim() >= 2 && a.sizes() == b.sizes() && a.scalar_type() == b.scalar_type(),
+              "copy_kv_blocks: a/b must be contiguous [L, NB, ...] GPU arrays of one shape and dtype");
+  auto ok = [&](const torch::Tensor& t) {
+    return t.is_cuda() && t.device() == a.device() && t.is_contiguous() &&
+           t.scalar_type() == at::kInt && t.dim() == 1;
+  };
+  TORCH_CHECK(ok(src) && ok(dst) && src.numel() == dst.numel(),
+              "copy_kv_blocks: src/dst must be contiguous int32 [n] on the arrays' device");
+  const int64_t n = src.numel(), L = a.size(0), NB = a.size(1);
+  if (n == 0 || L == 0 || NB == 0) return;
+  TORCH_CHECK(n <= INT32_MAX / 2 / L, "copy_kv_blocks: too many pairs");
+  const int64_t block_bytes = a.stride(1) * (int64_t)a.element_size();
+  const int64_t layer_stride = a.stride(0) * (int64_t)a.element_size();
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(a.data_ptr()) |
+                         reinterpret_cast<uintptr_t>(b.data_ptr()) |
+                         (uintptr_t)block_bytes | (uintptr_t)layer_stride;
+  const int vec = bits % 16 == 0 ? 16 : (bits % 4 == 0 ? 4 : 1);
+  launch_copy_kv_blocks(a.data_ptr(), b.data_ptr(), src.data_ptr<int>(), dst.data_ptr<int>(),
+                        (int)n, (int)L, layer_stride, block_bytes, vec, cur_stream());
 }
 
 // Shared body of the two decode-attention bindings. With `shared` false this
@@ -611,6 +692,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("silu_mul", &silu_mul);
   m.def("rope_inplace", &rope_inplace);
   m.def("store_kv", &store_kv);
+  m.def("rope_store_kv", &rope_store_kv);
+  m.def("copy_kv_blocks", &copy_kv_blocks);
   m.def("attn_decode_paged", &attn_decode_paged);
   m.def("attn_decode_paged_shared", &attn_decode_paged_shared);
   m.def("attn_prefill", &attn_prefill);

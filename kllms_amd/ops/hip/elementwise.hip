@@ -48,6 +48,38 @@ extern "C" __global__ void __launch_bounds__(256) rmsnorm_kernel(
 // --------------------------------------------------------------------------
 // Fused residual-add + RMSNorm: residual += x (written back), y = rmsnorm(residual)
 // --------------------------------------------------------------------------
+// ss + round(f * f): the square is rounded on its own and then added, the
+// form every build of this kernel has used (v_pk_mul_f32 + v_add_f32). Written
+// out so that both paths below keep it whatever the compiler would contract.
+__device__ __forceinline__ float add_square(float ss, float f) {
+#pragma clang fp contract(off)
+  const float sq = f * f;
+  return ss + sq;
+}
+
+// residual' = bf16(x + residual) of one 8-wide vector; returns the vector and
+// adds its squares to ss in element order.
+__device__ __forceinline__ bf16x8_vec add_round_vec(bf16x8_vec a, bf16x8_vec b, float& ss) {
+  bf16x8_vec s;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float f = bf16_to_f32(a[j]) + bf16_to_f32(b[j]);
+    s[j] = f32_to_bf16(f);
+    ss = add_square(ss, bf16_to_f32(s[j]));  // accumulate on the bf16-rounded sum
+  }
+  return s;
+}
+
+__device__ __forceinline__ bf16x8_vec scale_vec(bf16x8_vec s, bf16x8_vec w8, float inv_rms) {
+  bf16x8_vec o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    o[j] = f32_to_bf16(bf16_to_f32(s[j]) * inv_rms * bf16_to_f32(w8[j]));
+  return o;
+}
+
+#define ADD_RMSNORM_REG_VECS 4   // summed vectors a thread keeps in registers
+
 extern "C" __global__ void __launch_bounds__(256) fused_add_rmsnorm_kernel(
     bf16_t* __restrict__ out, const bf16_t* __restrict__ x,
     bf16_t* __restrict__ residual, const bf16_t* __restrict__ w, int n, float eps) {
@@ -60,18 +92,37 @@ extern "C" __global__ void __launch_bounds__(256) fused_add_rmsnorm_kernel(
   const int nvec = n / 8;
 
   float ss = 0.0f;
+  if (nvec <= ADD_RMSNORM_REG_VECS * (int)blockDim.x) {
+    // Register path (n <= 8192 at 256 threads): a thread's summed vectors stay
+    // in registers across the reduction, so the second pass reads nothing
+    // back, and the weight loads are issued with the inputs, ahead of the
+    // barrier. Same vectors per thread, same order of additions into ss.
+    bf16x8_vec s[ADD_RMSNORM_REG_VECS], wr[ADD_RMSNORM_REG_VECS];
+#pragma unroll
+    for (int u = 0; u < ADD_RMSNORM_REG_VECS; ++u) {
+      const int i = threadIdx.x + u * blockDim.x;
+      if (i < nvec) {
+        bf16x8_vec a = xv[i];
+        bf16x8_vec b = rv[i];
+        wr[u] = wv[i];
+        s[u] = add_round_vec(a, b, ss);
+        rv[i] = s[u];
+      }
+    }
+    ss = block_reduce_sum<4>(ss, red);
+    const float inv_rms = rsqrtf(ss / n + eps);
+#pragma unroll
+    for (int u = 0; u < ADD_RMSNORM_REG_VECS; ++u) {
+      const int i = threadIdx.x + u * blockDim.x;
+      if (i < nvec) outv[i] = scale_vec(s[u], wr[u], inv_rms);
+    }
+    return;
+  }
+
   for (int i = threadIdx.x; i < nvec; i += blockDim.x) {
     bf16x8_vec a = xv[i];
     bf16x8_vec b = rv[i];
-    bf16x8_vec s;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float f = bf16_to_f32(a[j]) + bf16_to_f32(b[j]);
-      s[j] = f32_to_bf16(f);
-      float fs = bf16_to_f32(s[j]);  // accumulate on the bf16-rounded sum
-      ss += fs * fs;
-    }
-    rv[i] = s;
+    rv[i] = add_round_vec(a, b, ss);
   }
   ss = block_reduce_sum<4>(ss, red);
   const float inv_rms = rsqrtf(ss / n + eps);
@@ -213,4 +264,152 @@ extern "C" __global__ void __launch_bounds__(256) store_kv_fp8_kernel(
       dst_v[d] = f32_to_fp8(bf16_to_f32(((const short*)src_v)[d]) * isv);
     }
   }
+}
+
+// --------------------------------------------------------------------------
+// RoPE + paged-KV store in one launch: rotates q and k in place exactly as
+// rope_kernel does, then writes the rotated (bf16-rounded) k and the untouched
+// v into the paged caches at slots[t] -- the bits rope_kernel followed by
+// store_kv_kernel / store_kv_fp8_kernel leave behind, without re-reading k.
+// One 64-lane wave per (token, head) row, 4 rows of one token per block;
+// grid (T, ceil((H + KVH) / 4)). A k-head wave also moves its head's v row.
+// Rows that share a slot (padded graph lanes) write the same few bytes in
+// any order, which is as harmless as it is with the two kernels.
+// --------------------------------------------------------------------------
+
+// The two rotation outputs in the form rope_kernel compiles to (one product
+// rounded on its own, the other fused into the sum); written out because the
+// compiler's contraction of `x1 * c - x2 * s` is not stable across kernels.
+__device__ __forceinline__ float rope_first(float x1, float x2, float c, float s) {
+#pragma clang fp contract(off)
+  const float p = x2 * s;
+  return __builtin_fmaf(x1, c, -p);
+}
+
+__device__ __forceinline__ float rope_second(float x1, float x2, float c, float s) {
+#pragma clang fp contract(off)
+  const float p = x2 * c;
+  return __builtin_fmaf(x1, s, p);
+}
+
+template <bool FP8>
+__device__ __forceinline__ void rope_store_kv_body(
+    bf16_t* __restrict__ q, bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+    void* __restrict__ k_cache, void* __restrict__ v_cache,
+    float* __restrict__ k_scale, float* __restrict__ v_scale,
+    const int64_t* __restrict__ positions, const float* __restrict__ cos_sin,
+    const int64_t* __restrict__ slots, int num_q_heads, int num_kv_heads, int head_dim,
+    int block_size, int q_tstride, int k_tstride, int v_tstride) {
+  const int t = blockIdx.x;
+  const int h = blockIdx.y * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (h >= num_q_heads + num_kv_heads) return;   // wave-uniform
+  const int half = head_dim / 2;
+  const int64_t pos = positions[t];
+  const float* cs = cos_sin + pos * head_dim;
+  const bool is_k = h >= num_q_heads;
+  const int g = h - num_q_heads;
+  short* base = reinterpret_cast<short*>(
+      is_k ? k + (int64_t)t * k_tstride + g * head_dim : q + (int64_t)t * q_tstride + h * head_dim);
+
+  if (!is_k) {
+    for (int i = lane; i < half; i += 64) {
+      const float c = cs[i], s = cs[half + i];
+      const float x1 = bf16_to_f32(base[i]), x2 = bf16_to_f32(base[half + i]);
+      base[i] = f32_to_bf16(rope_first(x1, x2, c, s));
+      base[half + i] = f32_to_bf16(rope_second(x1, x2, c, s));
+    }
+    return;
+  }
+
+  const int64_t slot = slots[t];
+  const int64_t blk = slot / block_size;
+  const int off = slot % block_size;
+  const int64_t srow = (blk * num_kv_heads + g) * block_size + off;
+  const short* src_v = reinterpret_cast<const short*>(v + (int64_t)t * v_tstride + g * head_dim);
+
+  if (!FP8) {
+    short* dst_k = reinterpret_cast<short*>(k_cache) + srow * head_dim;
+    for (int i = lane; i < half; i += 64) {
+      const float c = cs[i], s = cs[half + i];
+      const float x1 = bf16_to_f32(base[i]), x2 = bf16_to_f32(base[half + i]);
+      const short r1 = f32_to_bf16(rope_first(x1, x2, c, s));
+      const short r2 = f32_to_bf16(rope_second(x1, x2, c, s));
+      base[i] = r1;
+      base[half + i] = r2;
+      dst_k[i] = r1;
+      dst_k[half + i] = r2;
+    }
+    bf16x8_vec* dst_v = reinterpret_cast<bf16x8_vec*>(reinterpret_cast<short*>(v_cache) + srow * head_dim);
+    for (int dv = lane; dv < head_dim / 8; dv += 64)
+      dst_v[dv] = reinterpret_cast<const bf16x8_vec*>(src_v)[dv];
+    return;
+  }
+
+  // fp8: the arithmetic of store_kv_fp8_kernel on the rounded k. A lane keeps
+  // its first two rotation pairs in registers (all of them up to head_dim
+  // 256); beyond that it re-reads the elements it has just written itself.
+  float amax_k = 0.f, amax_v = 0.f;
+  auto rotate = [&](int i, short& r1, short& r2) {
+    const float c = cs[i], s = cs[half + i];
+    const float x1 = bf16_to_f32(base[i]), x2 = bf16_to_f32(base[half + i]);
+    r1 = f32_to_bf16(rope_first(x1, x2, c, s));
+    r2 = f32_to_bf16(rope_second(x1, x2, c, s));
+    base[i] = r1;
+    base[half + i] = r2;
+    amax_k = fmaxf(amax_k, fabsf(bf16_to_f32(r1)));
+    amax_k = fmaxf(amax_k, fabsf(bf16_to_f32(r2)));
+  };
+  short ra1 = 0, ra2 = 0, rb1 = 0, rb2 = 0;
+  if (lane < half) rotate(lane, ra1, ra2);
+  if (lane + 64 < half) rotate(lane + 64, rb1, rb2);
+  for (int i = lane + 128; i < half; i += 64) {
+    short r1, r2;
+    rotate(i, r1, r2);
+  }
+  for (int d = lane; d < head_dim; d += 64)
+    amax_v = fmaxf(amax_v, fabsf(bf16_to_f32(src_v[d])));
+  const float sk = fmaxf(wave_reduce_max(amax_k) * (1.0f / 448.0f), 1e-8f);
+  const float sv = fmaxf(wave_reduce_max(amax_v) * (1.0f / 448.0f), 1e-8f);
+  if (lane == 0) { k_scale[srow] = sk; v_scale[srow] = sv; }
+  const float isk = 1.0f / sk, isv = 1.0f / sv;
+  unsigned char* dst_k = reinterpret_cast<unsigned char*>(k_cache) + srow * head_dim;
+  unsigned char* dst_v = reinterpret_cast<unsigned char*>(v_cache) + srow * head_dim;
+  if (lane < half) {
+    dst_k[lane] = f32_to_fp8(bf16_to_f32(ra1) * isk);
+    dst_k[half + lane] = f32_to_fp8(bf16_to_f32(ra2) * isk);
+  }
+  if (lane + 64 < half) {
+    dst_k[lane + 64] = f32_to_fp8(bf16_to_f32(rb1) * isk);
+    dst_k[half + lane + 64] = f32_to_fp8(bf16_to_f32(rb2) * isk);
+  }
+  for (int i = lane + 128; i < half; i += 64) {
+    dst_k[i] = f32_to_fp8(bf16_to_f32(base[i]) * isk);
+    dst_k[half + i] = f32_to_fp8(bf16_to_f32(base[half + i]) * isk);
+  }
+  for (int d = lane; d < head_dim; d += 64)
+    dst_v[d] = f32_to_fp8(bf16_to_f32(src_v[d]) * isv);
+}
+
+extern "C" __global__ void __launch_bounds__(256) rope_store_kv_kernel(
+    bf16_t* __restrict__ q, bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+    bf16_t* __restrict__ k_cache, bf16_t* __restrict__ v_cache,
+    const int64_t* __restrict__ positions, const float* __restrict__ cos_sin,
+    const int64_t* __restrict__ slots, int num_q_heads, int num_kv_heads, int head_dim,
+    int block_size, int q_tstride, int k_tstride, int v_tstride) {
+  rope_store_kv_body<false>(q, k, v, k_cache, v_cache, nullptr, nullptr, positions, cos_sin,
+                            slots, num_q_heads, num_kv_heads, head_dim, block_size,
+                            q_tstride, k_tstride, v_tstride);
+}
+
+extern "C" __global__ void __launch_bounds__(256) rope_store_kv_fp8_kernel(
+    bf16_t* __restrict__ q, bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+    unsigned char* __restrict__ k_cache, unsigned char* __restrict__ v_cache,
+    float* __restrict__ k_scale, float* __restrict__ v_scale,
+    const int64_t* __restrict__ positions, const float* __restrict__ cos_sin,
+    const int64_t* __restrict__ slots, int num_q_heads, int num_kv_heads, int head_dim,
+    int block_size, int q_tstride, int k_tstride, int v_tstride) {
+  rope_store_kv_body<true>(q, k, v, k_cache, v_cache, k_scale, v_scale, positions, cos_sin,
+                           slots, num_q_heads, num_kv_heads, head_dim, block_size,
+                           q_tstride, k_tstride, v_tstride);
 }

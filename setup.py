@@ -20,6 +20,7 @@ SOURCES = [
     for f in (
         "bindings.hip",
         "elementwise.hip",
+        "kv_copy.hip",
         "attn_decode.hip",
         "attn_decode_shared.hip",
         "attn_prefill.hip",
