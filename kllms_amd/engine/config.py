@@ -208,6 +208,15 @@ class EngineConfig(BaseModel):
     # nothing changes. The environment variable KLLMS_PAGED_PREFILL_ATTN=1/0,
     # read once at engine construction, overrides this field.
     paged_prefill_attention: bool = False
+    # key splits of the paged prefill kernel (ignored unless
+    # paged_prefill_attention is on): 1 = every workgroup walks all of its
+    # sequence's keys; k >= 2 = up to k workgroups per q-tile group, each over
+    # a contiguous key range, merged by a reduce kernel — for a short tail
+    # after a long cached prefix, which alone leaves most CUs idle; 0 = auto:
+    # split only batches with fewer workgroups than the device has CUs. The
+    # environment variable KLLMS_PAGED_PREFILL_KEY_SPLITS, read once at engine
+    # construction, overrides this field.
+    paged_prefill_key_splits: int = 1
     # cross-request prefix caching: full prompt blocks are published to a
     # digest-keyed cache; later prompts sharing the prefix skip re-prefilling
     # it (LRU + eviction under allocator pressure)

@@ -205,6 +205,17 @@ class LLMEngine:
             raise ValueError(f"KLLMS_PAGED_PREFILL_ATTN must be 0 or 1, got {env_pp!r}")
         self.paged_prefill_attention = (
             config.paged_prefill_attention if not env_pp else env_pp == "1")
+        # its key splits (1 none, k >= 2 forced, 0 auto): config field,
+        # overridden by KLLMS_PAGED_PREFILL_KEY_SPLITS (read once, here)
+        env_ks = os.environ.get("KLLMS_PAGED_PREFILL_KEY_SPLITS")
+        if env_ks not in (None, "") and not env_ks.isdigit():
+            raise ValueError(
+                f"KLLMS_PAGED_PREFILL_KEY_SPLITS must be an integer >= 0, got {env_ks!r}")
+        key_splits = int(env_ks) if env_ks else config.paged_prefill_key_splits
+        if isinstance(key_splits, bool) or not isinstance(key_splits, int) or key_splits < 0:
+            raise ValueError(
+                f"paged_prefill_key_splits must be an integer >= 0, got {key_splits!r}")
+        self.paged_prefill_key_splits = key_splits
         # fp8 (e4m3) layer weights: config field, overridden by
         # KLLMS_WEIGHT_DTYPE=bf16/fp8_e4m3 (read once, here)
         env_wd = os.environ.get("KLLMS_WEIGHT_DTYPE")
@@ -593,6 +604,11 @@ class LLMEngine:
         self._fork_and_sample(requests, parent_seqs, prefill_logits, streams)
         return outputs
 
+    def _local_q_heads(self) -> int:
+        """q-heads of one attention launch on this rank (the head dimension of
+        the grid the paged prefill planner fills the device with)."""
+        return max(1, self.arch.num_heads // self.ctx.world_size)
+
     def _prefill_tails(self, seqs: List[SequenceKV], ids_list: List[List[int]],
                        starts: List[int]) -> torch.Tensor:
         """One decode-mode forward over the concatenated TAILS of several
@@ -620,7 +636,9 @@ class LLMEngine:
             # the per-token [T, nb] table and context lengths
             attn = dict(extend=ops.build_paged_prefill(
                 [len(ids) - start for ids, start in zip(ids_list, starts)], starts,
-                [seq.blocks for seq in seqs], dev, self.kv.block_size))
+                [seq.blocks for seq in seqs], dev, self.kv.block_size,
+                key_splits=self.paged_prefill_key_splits,
+                num_q_heads=self._local_q_heads()))
         else:
             max_nb = max(len(b) for b in bt_blocks)
             bt = torch.zeros((len(bt_blocks), max_nb), dtype=torch.int32)
@@ -737,7 +755,9 @@ class LLMEngine:
             # the chunk as ONE sequence of the tiled paged kernel (its own
             # table row, `start` keys already cached), not end-start decode rows
             attn = dict(extend=ops.build_paged_prefill(
-                [end - start], [start], [seq.blocks], dev, self.kv.block_size))
+                [end - start], [start], [seq.blocks], dev, self.kv.block_size,
+                key_splits=self.paged_prefill_key_splits,
+                num_q_heads=self._local_q_heads()))
         else:
             nb = len(seq.blocks)
             bt = (

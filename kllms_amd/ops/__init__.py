@@ -323,13 +323,28 @@ class PagedPrefill:
     range of each sequence's new tokens; q_start [n_seq] — keys already in the
     cache; block_tables [n_seq, max_blocks] — ONE table row per sequence;
     grp_seq [G] and grp_qpos0 [G * 8] — per workgroup its sequence and the
-    first row (relative to cu_q) of each wave's 32-row q-tile, -1 = idle."""
+    first row (relative to cu_q) of each wave's 32-row q-tile, -1 = idle.
+
+    With key splits (``key_splits`` != 1 chose to split at least one
+    sequence; None / 0 / 1 otherwise): grp_krange [G * 2] — the workgroup's
+    key range [kbeg, kend), kbeg a multiple of 64; grp_split [G] — its split
+    index, -1 for a workgroup of an unsplit sequence (whole range, writes the
+    output itself); seq_nsplit [n_seq] — splits of the sequence (1 = unsplit);
+    seq_ws_base [n_seq] — its first partial slot, row i / split j of the
+    sequence owning slot ``base + i * nsplit + j``; ws_rows — slots in all;
+    max_splits — the largest seq_nsplit."""
 
     cu_q: torch.Tensor
     q_start: torch.Tensor
     block_tables: torch.Tensor
     grp_seq: torch.Tensor
     grp_qpos0: torch.Tensor
+    grp_krange: Optional[torch.Tensor] = None
+    grp_split: Optional[torch.Tensor] = None
+    seq_nsplit: Optional[torch.Tensor] = None
+    seq_ws_base: Optional[torch.Tensor] = None
+    ws_rows: int = 0
+    max_splits: int = 1
 
     @property
     def n_seq(self) -> int:
@@ -339,13 +354,67 @@ class PagedPrefill:
     def n_groups(self) -> int:
         return int(self.grp_seq.shape[0])
 
+    @property
+    def has_splits(self) -> bool:
+        return self.grp_split is not None
+
 
 PAGED_PREFILL_WAVES = 8     # q-tile slots per workgroup (attn_prefill_paged.hip)
 PAGED_PREFILL_QBLK = 32
+PAGED_PREFILL_KVBLK = 64    # keys per round: the unit key ranges are cut in
+PAGED_PREFILL_MAX_SPLITS = 64
+# partial workspace budget: (128 + 2) fp32 per (slot, q-head); splits are
+# reduced rather than exceed it
+PAGED_PREFILL_WS_BYTES = 256 << 20
+PAGED_PREFILL_WS_CELL_BYTES = (128 + 2) * 4
+# the budget is checked against this many q-heads when the caller names none
+PAGED_PREFILL_WS_HEADS = 128
+# auto (key_splits=0) tunables, from the "Paged prefill attention: key splits"
+# table of profiles/README.md: a split keeps at least this many 64-key rounds
+# (64 rows after 1024 keys, 17 rounds: 8 splits of 2-3 rounds took 21.9 us, 4
+# splits 23.9 us, 16 splits of 1-2 rounds 36.3 us — below 2 rounds the fixed
+# cost of a workgroup, its Q fragments, first unoverlapped gather, partial
+# write and merge, outweighs the shorter loop), and a batch that is split
+# packs all of a sequence's q-tiles (up to 8) into one workgroup, so each key
+# range is read once per head (the packing every forced count was timed with).
+PAGED_PREFILL_AUTO_MIN_ROUNDS = 2
+PAGED_PREFILL_AUTO_TILES = 8
+
+
+def _device_cu_count(device) -> Optional[int]:
+    """Compute units of ``device`` from its properties; None off the GPU."""
+    dev = torch.device(device)
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        return None
+    return int(torch.cuda.get_device_properties(dev).multi_processor_count)
+
+
+def _auto_key_splits(q_lens, q_starts, tiles_per_group, default_tpg, num_q_heads, num_cus):
+    """(per-sequence split counts, tiles per group) of auto mode, or None to
+    keep the unsplit plan."""
+    NW, QB, KB = PAGED_PREFILL_WAVES, PAGED_PREFILL_QBLK, PAGED_PREFILL_KVBLK
+    if num_cus is None:
+        return None
+    tiles = [(L + QB - 1) // QB for L in q_lens]
+    groups = sum((t + default_tpg - 1) // default_tpg for t in tiles)
+    if groups * num_q_heads >= num_cus:
+        return None
+    tpg = PAGED_PREFILL_AUTO_TILES if tiles_per_group is None else tiles_per_group
+    packed = sum((t + tpg - 1) // tpg for t in tiles)
+    k = min(num_cus // (packed * num_q_heads), PAGED_PREFILL_MAX_SPLITS)
+    per_seq = []
+    for L, s0 in zip(q_lens, q_starts):
+        rounds = (s0 + L + KB - 1) // KB
+        per_seq.append(max(1, min(k, rounds // PAGED_PREFILL_AUTO_MIN_ROUNDS)))
+    if max(per_seq) < 2:
+        return None
+    return per_seq, tpg
 
 
 def build_paged_prefill(q_lens, q_starts, block_lists, device, block_size: int,
-                        tiles_per_group: Optional[int] = None) -> PagedPrefill:
+                        tiles_per_group: Optional[int] = None, key_splits: int = 1,
+                        num_q_heads: Optional[int] = None,
+                        num_cus: Optional[int] = None) -> PagedPrefill:
     """Build ``PagedPrefill`` from Python lists in one host pass: sequence s
     appends ``q_lens[s]`` >= 1 tokens after ``q_starts[s]`` >= 0 cached keys and
     owns the physical blocks ``block_lists[s]`` (of ``block_size`` slots).
@@ -355,10 +424,30 @@ def build_paged_prefill(q_lens, q_starts, block_lists, device, block_size: int,
     ``tiles_per_group`` (1..8) is how many tiles share a workgroup's K/V
     staging; None picks 8 once the batch has 64 tiles and fewer below, so that
     a short append still spreads over enough workgroups. Raises when a
-    sequence's ``start + len`` does not fit its blocks."""
-    NW, QB = PAGED_PREFILL_WAVES, PAGED_PREFILL_QBLK
+    sequence's ``start + len`` does not fit its blocks.
+
+    ``key_splits``: 1 — every workgroup walks all of its keys (the fields
+    above only). k >= 2 — each sequence's ``ceil((start + len) / 64)`` rounds
+    are spread as evenly as possible over up to k contiguous key ranges (never
+    more ranges than rounds, at most 64); every q-tile group then has one
+    workgroup per range, which writes a partial that a reduce kernel merges.
+    0 — auto: split only when the unsplit plan has fewer workgroups
+    (groups x ``num_q_heads``, required here) than the device has compute
+    units (``num_cus``, default: the device's properties; never on the CPU);
+    then all of a sequence's q-tiles share a workgroup and the split count
+    brings the workgroup count up to the CU count, each split keeping at least
+    ``PAGED_PREFILL_AUTO_MIN_ROUNDS`` rounds. Where auto does not split it
+    returns exactly the ``key_splits=1`` plan. Split counts are reduced until
+    the partial workspace fits ``PAGED_PREFILL_WS_BYTES``."""
+    NW, QB, KB = PAGED_PREFILL_WAVES, PAGED_PREFILL_QBLK, PAGED_PREFILL_KVBLK
     if not (len(q_lens) == len(q_starts) == len(block_lists)) or len(q_lens) == 0:
         raise ValueError("build_paged_prefill: need one q_len, q_start and block list per sequence")
+    if isinstance(key_splits, bool) or not isinstance(key_splits, int) or key_splits < 0:
+        raise ValueError(f"build_paged_prefill: key_splits must be an integer >= 0, got {key_splits!r}")
+    if key_splits == 0 and num_q_heads is None:
+        raise ValueError("build_paged_prefill: key_splits=0 (auto) needs num_q_heads")
+    if num_q_heads is not None and num_q_heads < 1:
+        raise ValueError(f"build_paged_prefill: num_q_heads {num_q_heads} out of range")
     n_tiles = 0
     for L, s0, blocks in zip(q_lens, q_starts, block_lists):
         if L < 1 or s0 < 0:
@@ -368,24 +457,61 @@ def build_paged_prefill(q_lens, q_starts, block_lists, device, block_size: int,
                 f"build_paged_prefill: start {s0} + len {L} exceeds the sequence's "
                 f"{len(blocks)} blocks of {block_size}")
         n_tiles += (L + QB - 1) // QB
-    if tiles_per_group is None:
-        tiles_per_group = min(NW, max(1, n_tiles // 8))
-    if not 1 <= tiles_per_group <= NW:
+    if tiles_per_group is not None and not 1 <= tiles_per_group <= NW:
         raise ValueError(f"build_paged_prefill: tiles_per_group must be 1..{NW}")
+    default_tpg = min(NW, max(1, n_tiles // 8))
+    nsplit = [1] * len(q_lens)
+    if key_splits == 0:
+        auto = _auto_key_splits(q_lens, q_starts, tiles_per_group, default_tpg, num_q_heads,
+                                num_cus if num_cus is not None else _device_cu_count(device))
+        if auto is not None:
+            nsplit, tiles_per_group = auto
+    elif key_splits >= 2:
+        nsplit = [min(key_splits, PAGED_PREFILL_MAX_SPLITS, (s0 + L + KB - 1) // KB)
+                  for L, s0 in zip(q_lens, q_starts)]
+    if tiles_per_group is None:
+        tiles_per_group = default_tpg
+    # the workspace budget: take a split off the most-split sequences until
+    # the partials fit
+    cell = PAGED_PREFILL_WS_CELL_BYTES * (num_q_heads or PAGED_PREFILL_WS_HEADS)
+    while sum(L * k for L, k in zip(q_lens, nsplit) if k > 1) * cell > PAGED_PREFILL_WS_BYTES:
+        top = max(nsplit)
+        nsplit = [k - 1 if k == top else k for k in nsplit]
+    split = max(nsplit) > 1
     max_nb = max(len(b) for b in block_lists)
     cu = [0]
-    table, grp_seq, grp_qpos0 = [], [], []
-    for s, (L, blocks) in enumerate(zip(q_lens, block_lists)):
+    table, grp_seq, grp_qpos0, grp_krange, grp_split, ws_base = [], [], [], [], [], []
+    ws_rows = 0
+    for s, (L, s0, blocks) in enumerate(zip(q_lens, q_starts, block_lists)):
         cu.append(cu[-1] + L)
         table.append(list(blocks) + [0] * (max_nb - len(blocks)))
+        k = nsplit[s]
+        if k > 1:
+            # rounds spread evenly: the first (rounds % k) ranges get one more
+            rounds = (s0 + L + KB - 1) // KB
+            edges = [(j * (rounds // k) + min(j, rounds % k)) * KB for j in range(k + 1)]
+            ranges = [(edges[j], min(edges[j + 1], s0 + L), j) for j in range(k)]
+            ws_base.append(ws_rows)
+            ws_rows += L * k
+        else:
+            ranges = [(0, 0x7FFFFFFF, -1)]
+            ws_base.append(0)
         tiles = list(range(0, L, QB))
         for g0 in range(0, len(tiles), tiles_per_group):
             grp = tiles[g0: g0 + tiles_per_group]
-            grp_seq.append(s)
-            grp_qpos0.extend(grp + [-1] * (NW - len(grp)))
+            for kbeg, kend, j in ranges:
+                grp_seq.append(s)
+                grp_qpos0.extend(grp + [-1] * (NW - len(grp)))
+                grp_krange.extend((kbeg, kend))
+                grp_split.append(j)
     t = lambda x: torch.tensor(x, dtype=torch.int32, device=device)
-    return PagedPrefill(cu_q=t(cu), q_start=t(list(q_starts)), block_tables=t(table),
+    meta = PagedPrefill(cu_q=t(cu), q_start=t(list(q_starts)), block_tables=t(table),
                         grp_seq=t(grp_seq), grp_qpos0=t(grp_qpos0))
+    if split:
+        meta.grp_krange, meta.grp_split = t(grp_krange), t(grp_split)
+        meta.seq_nsplit, meta.seq_ws_base = t(nsplit), t(ws_base)
+        meta.ws_rows, meta.max_splits = ws_rows, max(nsplit)
+    return meta
 
 
 def attn_prefill_paged(
@@ -402,16 +528,31 @@ def attn_prefill_paged(
     all read from the cache (``store_kv`` has already written the new ones).
     On the GPU this is the MFMA kernel of attn_prefill_paged.hip; elsewhere
     ``torch_ref.attn_prefill_paged``, which is ``attn_decode_paged`` over the
-    per-token rows."""
+    per-token rows. Metadata with key splits runs the split kernel and its
+    reduce over a workspace allocated here (prefill is not graph-captured);
+    elsewhere ``torch_ref.attn_prefill_paged_split`` walks the same plan."""
     if q.is_cuda and not _force_torch():
         out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
         none = torch.empty(0, dtype=torch.float32, device=q.device)
+        ks = k_scale if k_scale is not None else none
+        vs = v_scale if v_scale is not None else none
+        if meta.has_splits:
+            H = q.shape[1]
+            part_o = torch.empty((meta.ws_rows, H, 128), dtype=torch.float32, device=q.device)
+            part_ml = torch.empty((meta.ws_rows, H, 2), dtype=torch.float32, device=q.device)
+            _hip_or_raise().attn_prefill_paged_split(
+                out, q, k_cache, v_cache, meta.block_tables, meta.cu_q, meta.q_start,
+                meta.grp_seq, meta.grp_qpos0, meta.grp_krange, meta.grp_split,
+                meta.seq_nsplit, meta.seq_ws_base, part_o, part_ml, meta.ws_rows,
+                meta.max_splits, scale, ks, vs)
+            return out
         _hip_or_raise().attn_prefill_paged(
             out, q, k_cache, v_cache, meta.block_tables, meta.cu_q, meta.q_start,
-            meta.grp_seq, meta.grp_qpos0, scale,
-            k_scale if k_scale is not None else none,
-            v_scale if v_scale is not None else none)
+            meta.grp_seq, meta.grp_qpos0, scale, ks, vs)
         return out
+    if meta.has_splits:
+        return torch_ref.attn_prefill_paged_split(q, k_cache, v_cache, meta, scale,
+                                                  k_scale, v_scale)
     return torch_ref.attn_prefill_paged(q, k_cache, v_cache, meta.block_tables, meta.cu_q,
                                         meta.q_start, scale, k_scale, v_scale)
 

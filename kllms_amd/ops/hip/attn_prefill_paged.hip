@@ -28,10 +28,22 @@
 // Robustness: the sequence index, block ids and table indices are clamped,
 // the key loop never passes max_blocks * block_size, rows past q_len are
 // never stored.
+//
+// Key splits (SP = PPSplit): a workgroup also gets a key range
+// [kbeg, kend), kbeg a multiple of 64, and walks only the rounds inside it. A
+// workgroup of a split sequence (grp_split >= 0) does not normalise: per
+// (row, head, split) it writes the fp32 unnormalised O[128] and (m, l) — its
+// softmax reference and the sum of p relative to it — to a workspace slot
+// (seq_ws_base[s] + row * seq_nsplit[s] + split), and attn_prefill_paged_reduce
+// merges a row's slots in split order. A row that sees no key of the range
+// writes (m, l, O) = (-inf, 0, 0). Workgroups with grp_split = -1 keep the
+// direct epilogue, so one launch serves split and unsplit sequences. kbeg,
+// kend, the split index and the slot are clamped like the rest.
 
 #include "common.h"
 
 typedef __bf16 bf16x8_mfma __attribute__((ext_vector_type(8)));
+typedef float pp_f32x2 __attribute__((ext_vector_type(2)));
 
 #define PP_QBLK 32
 #define PP_KVBLK 64                // staged keys per barrier round (2 MFMA sub-tiles)
@@ -48,7 +60,25 @@ template <bool FP8> struct PPRegs;
 template <> struct PPRegs<false> { bf16x8_vec ka, kb, va, vb; };
 template <> struct PPRegs<true> { u8x16_vec k8, v8; float ks, vs; };
 
-template <bool FP8>
+// split-mode arguments: the plan's per-workgroup and per-sequence tensors and
+// the partial workspace
+struct PPSplit {
+  static constexpr bool enabled = true;
+  const int* grp_krange;     // [G * 2]: kbeg, kend
+  const int* grp_split;      // [G]: split index, -1 = direct epilogue
+  const int* seq_nsplit;     // [n_seq]
+  const int* seq_ws_base;    // [n_seq]: first workspace slot of the sequence
+  float* part_o;             // [ws_rows, H, 128]
+  float* part_ml;            // [ws_rows, H, 2]
+  int ws_rows;
+  int max_splits;
+};
+
+struct PPNoSplit { static constexpr bool enabled = false; };
+
+// SP = PPNoSplit: the whole key range and the direct epilogue; the trailing
+// argument is empty and every split branch is compiled out
+template <bool FP8, typename SP = PPNoSplit>
 __global__ __launch_bounds__(64 * PP_NWAVES) void attn_prefill_paged_t(
     bf16_t* __restrict__ out,            // [T, H, 128] contiguous
     const bf16_t* __restrict__ q,        // [T, H, 128], token stride q_tstride
@@ -62,7 +92,8 @@ __global__ __launch_bounds__(64 * PP_NWAVES) void attn_prefill_paged_t(
     const int* __restrict__ grp_seq,        // [G]
     const int* __restrict__ grp_qpos0,      // [G * 8], -1 = idle wave
     float scale, int n_seq, int total_rows, int num_q_heads, int num_kv_heads,
-    int num_blocks, int block_size, int max_blocks, int q_tstride) {
+    int num_blocks, int block_size, int max_blocks, int q_tstride, SP sp) {
+  constexpr bool SPLIT = SP::enabled;
   const int grp = blockIdx.x;
   const int h = blockIdx.y;
   const int g_kv = h / (num_q_heads / num_kv_heads);
@@ -110,7 +141,15 @@ __global__ __launch_bounds__(64 * PP_NWAVES) void attn_prefill_paged_t(
     if (qp0 >= 0 && qp0 < qlen) kv_end_grp = max(kv_end_grp, start + min(qlen, qp0 + PP_QBLK));
   }
   kv_end_grp = min(kv_end_grp, kv_cap);
-  const int kv_end_me = active ? min(start + min(qlen, qpos0 + PP_QBLK), kv_cap) : 0;
+  int kv_end_me = active ? min(start + min(qlen, qpos0 + PP_QBLK), kv_cap) : 0;
+  int kbeg = 0;
+  if constexpr (SPLIT) {
+    // the workgroup's key range, cut to the causal bound
+    const int kend = max(sp.grp_krange[grp * 2 + 1], 0);
+    kbeg = min(max(sp.grp_krange[grp * 2], 0), kv_cap) & ~(PP_KVBLK - 1);
+    kv_end_grp = min(kv_end_grp, kend);
+    kv_end_me = min(kv_end_me, kend);
+  }
 
   const int* bt = block_tables + (int64_t)seq * max_blocks;
   const int st_key = tid >> 3;               // one key per 8 threads
@@ -168,9 +207,9 @@ __global__ __launch_bounds__(64 * PP_NWAVES) void attn_prefill_paged_t(
   };
 
   PPRegs<FP8> regs;
-  load_round(0, regs);
+  load_round(kbeg, regs);
 
-  for (int kt00 = 0; kt00 < kv_end_grp; kt00 += PP_KVBLK) {
+  for (int kt00 = kbeg; kt00 < kv_end_grp; kt00 += PP_KVBLK) {
     const int nkeys_blk = min(PP_KVBLK, kv_end_grp - kt00);
     store_round(regs);
     __syncthreads();
@@ -221,7 +260,10 @@ __global__ __launch_bounds__(64 * PP_NWAVES) void attn_prefill_paged_t(
       // then bounded by e^THR); decided BEFORE this tile's P is exponentiated
       const float DEFER_THR = 8.0f;
       float m_new, alpha;
-      if (tmax <= m_run + DEFER_THR) {       // first tile: m_run=-inf fails this
+      // first visible key: m_run=-inf fails this. A row that has seen no key
+      // yet and sees none here (a split range above its causal limit) has
+      // tmax = m_run = -inf, keeps m_run and adds p = 0.
+      if (tmax <= m_run + DEFER_THR) {
         m_new = m_run;
         alpha = 1.0f;
       } else {
@@ -291,6 +333,39 @@ __global__ __launch_bounds__(64 * PP_NWAVES) void attn_prefill_paged_t(
     auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
     l_run = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
   }
+  if constexpr (SPLIT) {
+    const int split = sp.grp_split[grp];            // workgroup-uniform
+    if (split >= 0) {
+      // partial of (row, head, split): unnormalised O, reference m, sum l. A
+      // wave whose loop never ran writes (-inf, 0, 0) from its initial state.
+      if (active && my_qpos < qlen) {
+        const int nsplit = min(max(sp.seq_nsplit[seq], 1), sp.max_splits);
+        int64_t slot = (int64_t)sp.seq_ws_base[seq] + (int64_t)my_qpos * nsplit +
+                       min(split, nsplit - 1);
+        slot = min(max(slot, (int64_t)0), (int64_t)sp.ws_rows - 1);
+        const int64_t cell = slot * num_q_heads + h;
+        float* po = sp.part_o + cell * 128;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+#pragma unroll
+          for (int g2 = 0; g2 < 4; ++g2) {
+            const int d0 = dt * 32 + 8 * g2 + 4 * half;
+            f32x4 v4;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v4[j] = o_acc[dt][4 * g2 + j];
+            *reinterpret_cast<f32x4*>(po + d0) = v4;
+          }
+        }
+        if (half == 0) {
+          pp_f32x2 ml;
+          ml[0] = m_run;
+          ml[1] = l_run;
+          *reinterpret_cast<pp_f32x2*>(sp.part_ml + cell * 2) = ml;
+        }
+      }
+      return;
+    }
+  }
   if (active && my_qpos < qlen) {
     const float inv_l = (l_run > 0.0f) ? 1.0f / l_run : 0.0f;
     bf16_t* op = out + (((int64_t)(row0 + my_qpos)) * num_q_heads + h) * 128;
@@ -311,6 +386,62 @@ __global__ __launch_bounds__(64 * PP_NWAVES) void attn_prefill_paged_t(
   }
 }
 
+// Merge of the split partials: block (t, 8-head group), 32 threads per head,
+// 4 dims per thread. With j over the row's splits in index order and
+// w_j = exp(m_j - max_j m_j) (0 for an empty partial: l_j = 0 or m_j = -inf),
+// out = sum_j w_j O_j / sum_j w_j l_j, zeros when the denominator is 0. The
+// order is fixed, so the result does not depend on which workgroup finished
+// first. Rows of unsplit sequences are left alone.
+#define PP_RED_HEADS 8
+__global__ __launch_bounds__(32 * PP_RED_HEADS) void attn_prefill_paged_reduce(
+    bf16_t* __restrict__ out, const float* __restrict__ part_o,
+    const float* __restrict__ part_ml, const int* __restrict__ cu_q,
+    const int* __restrict__ seq_nsplit, const int* __restrict__ seq_ws_base,
+    int n_seq, int total_rows, int num_q_heads, int ws_rows, int max_splits) {
+  const int t = blockIdx.x;
+  const int h = blockIdx.y * PP_RED_HEADS + (threadIdx.x >> 5);
+  const int d0 = (threadIdx.x & 31) * 4;
+  if (t >= total_rows || h >= num_q_heads) return;
+  // the sequence holding packed row t: last s with cu_q[s] <= t
+  int lo = 0, hi = n_seq - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (cu_q[mid] <= t) lo = mid; else hi = mid - 1;
+  }
+  const int seq = lo;
+  const int row = t - cu_q[seq];
+  const int nsplit = min(seq_nsplit[seq], max_splits);
+  if (nsplit < 2 || row < 0 || t >= cu_q[seq + 1]) return;
+  const int64_t slot0 = (int64_t)seq_ws_base[seq] + (int64_t)row * nsplit;
+  auto cell_of = [&](int j) {
+    const int64_t slot = min(max(slot0 + j, (int64_t)0), (int64_t)ws_rows - 1);
+    return slot * num_q_heads + h;
+  };
+  float m_all = -INFINITY;
+  for (int j = 0; j < nsplit; ++j) {
+    const pp_f32x2 ml = *reinterpret_cast<const pp_f32x2*>(part_ml + cell_of(j) * 2);
+    if (ml[1] > 0.0f) m_all = fmaxf(m_all, ml[0]);
+  }
+  f32x4 acc = {};
+  float den = 0.0f;
+  for (int j = 0; j < nsplit; ++j) {
+    const int64_t cell = cell_of(j);
+    const pp_f32x2 ml = *reinterpret_cast<const pp_f32x2*>(part_ml + cell * 2);
+    if (!(ml[1] > 0.0f) || ml[0] == -INFINITY) continue;     // empty partial
+    const float w = __expf(ml[0] - m_all);
+    const f32x4 o = *reinterpret_cast<const f32x4*>(part_o + cell * 128 + d0);
+    den += w * ml[1];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i] += w * o[i];
+  }
+  const float inv = (den > 0.0f) ? 1.0f / den : 0.0f;
+  uint64_t word = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    word |= ((uint64_t)(uint16_t)f32_to_bf16(acc[i] * inv)) << (16 * i);
+  *reinterpret_cast<uint64_t*>((short*)(out + ((int64_t)t * num_q_heads + h) * 128) + d0) = word;
+}
+
 // host-side launcher; an empty grid is the caller's to skip
 extern "C" void launch_attn_prefill_paged(
     bf16_t* out, const bf16_t* q, const void* k_cache, const void* v_cache,
@@ -326,12 +457,45 @@ extern "C" void launch_attn_prefill_paged(
                        out, q, (const char*)k_cache, (const char*)v_cache, k_scale, v_scale,
                        block_tables, cu_q, q_start, grp_seq, grp_qpos0, scale, n_seq,
                        total_rows, num_q_heads, num_kv_heads, num_blocks, block_size,
-                       max_blocks, q_tstride);
+                       max_blocks, q_tstride, PPNoSplit{});
   } else {
     hipLaunchKernelGGL((attn_prefill_paged_t<false>), grid, dim3(64 * PP_NWAVES), 0, stream,
                        out, q, (const char*)k_cache, (const char*)v_cache, k_scale, v_scale,
                        block_tables, cu_q, q_start, grp_seq, grp_qpos0, scale, n_seq,
                        total_rows, num_q_heads, num_kv_heads, num_blocks, block_size,
-                       max_blocks, q_tstride);
+                       max_blocks, q_tstride, PPNoSplit{});
   }
+}
+
+// split launch + merge; the caller has checked the workspace against ws_rows
+extern "C" void launch_attn_prefill_paged_split(
+    bf16_t* out, const bf16_t* q, const void* k_cache, const void* v_cache,
+    const float* k_scale, const float* v_scale, const int* block_tables,
+    const int* cu_q, const int* q_start, const int* grp_seq, const int* grp_qpos0,
+    const int* grp_krange, const int* grp_split, const int* seq_nsplit,
+    const int* seq_ws_base, float* part_o, float* part_ml, int ws_rows, int max_splits,
+    float scale, int n_seq, int total_rows, int num_q_heads, int num_kv_heads,
+    int num_blocks, int block_size, int max_blocks, int q_tstride, int n_groups,
+    int cache_fp8, hipStream_t stream) {
+  if (n_groups <= 0 || n_seq <= 0 || total_rows <= 0 || ws_rows <= 0) return;
+  const PPSplit sp{grp_krange, grp_split, seq_nsplit, seq_ws_base, part_o, part_ml,
+                   ws_rows, max_splits};
+  const dim3 grid(n_groups, num_q_heads);
+  if (cache_fp8) {
+    hipLaunchKernelGGL((attn_prefill_paged_t<true, PPSplit>), grid, dim3(64 * PP_NWAVES), 0, stream,
+                       out, q, (const char*)k_cache, (const char*)v_cache, k_scale, v_scale,
+                       block_tables, cu_q, q_start, grp_seq, grp_qpos0, scale, n_seq,
+                       total_rows, num_q_heads, num_kv_heads, num_blocks, block_size,
+                       max_blocks, q_tstride, sp);
+  } else {
+    hipLaunchKernelGGL((attn_prefill_paged_t<false, PPSplit>), grid, dim3(64 * PP_NWAVES), 0, stream,
+                       out, q, (const char*)k_cache, (const char*)v_cache, k_scale, v_scale,
+                       block_tables, cu_q, q_start, grp_seq, grp_qpos0, scale, n_seq,
+                       total_rows, num_q_heads, num_kv_heads, num_blocks, block_size,
+                       max_blocks, q_tstride, sp);
+  }
+  const dim3 rgrid(total_rows, (num_q_heads + PP_RED_HEADS - 1) / PP_RED_HEADS);
+  hipLaunchKernelGGL(attn_prefill_paged_reduce, rgrid, dim3(32 * PP_RED_HEADS), 0, stream,
+                     out, part_o, part_ml, cu_q, seq_nsplit, seq_ws_base, n_seq, total_rows,
+                     num_q_heads, ws_rows, max_splits);
 }

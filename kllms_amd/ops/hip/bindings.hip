@@ -19,6 +19,7 @@ extern "C" void launch_copy_kv_blocks(void*, void*, const int*, const int*, int,
 extern "C" void launch_attn_decode_partial(float*, const bf16_t*, const void*, const void*, const float*, const float*, const int*, const int*, const int*, float, int, int, int, int, int, int, int, int, int, hipStream_t);
 extern "C" void launch_attn_decode_shared(float*, const bf16_t*, const void*, const void*, const float*, const float*, const int*, const int*, const int*, const int*, float, int, int, int, int, int, int, int, int, int, int, hipStream_t);
 extern "C" void launch_attn_prefill_paged(bf16_t*, const bf16_t*, const void*, const void*, const float*, const float*, const int*, const int*, const int*, const int*, const int*, float, int, int, int, int, int, int, int, int, int, int, hipStream_t);
+extern "C" void launch_attn_prefill_paged_split(bf16_t*, const bf16_t*, const void*, const void*, const float*, const float*, const int*, const int*, const int*, const int*, const int*, const int*, const int*, const int*, const int*, float*, float*, int, int, float, int, int, int, int, int, int, int, int, int, int, hipStream_t);
 extern "C" __global__ void attn_decode_reduce_kernel(bf16_t*, const float*, const int*, int, int, int, int);
 extern "C" __global__ void attn_prefill_kernel(bf16_t*, const bf16_t*, const bf16_t*, const bf16_t*, const int*, const int*, const int*, float, int, int, int, int);  // grouped: [G], [G], [G*8]
 extern "C" __global__ void sample_kernel(int64_t*, float*, const float*, const float*, const float*, const int*, const int64_t*, const int64_t*, const uint32_t*, int, float*);
@@ -351,6 +352,87 @@ void attn_prefill_paged(torch::Tensor out, torch::Tensor q, torch::Tensor k_cach
       grp_seq.data_ptr<int>(), grp_qpos0.data_ptr<int>(), (float)scale, n_seq, T, H, KVH,
       (int)k_cache.size(0), BS, (int)block_tables.size(1), (int)q.stride(0), n_groups,
       cache_fp8, cur_stream());
+}
+
+// attn_prefill_paged with the keys of some sequences split across workgroups
+// (ops.build_paged_prefill(key_splits=...)): grp_krange [G*2] is each
+// workgroup's key range, grp_split [G] its split index (-1: the sequence is
+// unsplit and the workgroup writes out directly), seq_nsplit / seq_ws_base
+// [n_seq] the sequence's split count and first workspace slot. part_o
+// [>= ws_rows, H, 128] and part_ml [>= ws_rows, H, 2] (fp32) take the
+// partials, which a second kernel merges into out. ws_rows and max_splits are
+// the plan's slot count and largest split count.
+void attn_prefill_paged_split(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
+                              torch::Tensor v_cache, torch::Tensor block_tables,
+                              torch::Tensor cu_q, torch::Tensor q_start, torch::Tensor grp_seq,
+                              torch::Tensor grp_qpos0, torch::Tensor grp_krange,
+                              torch::Tensor grp_split, torch::Tensor seq_nsplit,
+                              torch::Tensor seq_ws_base, torch::Tensor part_o,
+                              torch::Tensor part_ml, int64_t ws_rows, int64_t max_splits,
+                              double scale, torch::Tensor k_scale, torch::Tensor v_scale) {
+  CHECK_BF16_CONTIG(out); CHECK_BF16_ROWS(q); CHECK_KV_CACHE(k_cache); CHECK_KV_CACHE(v_cache);
+  TORCH_CHECK(k_cache.dim() == 4 && v_cache.sizes() == k_cache.sizes() &&
+                  v_cache.scalar_type() == k_cache.scalar_type(),
+              "attn_prefill_paged_split: k_cache/v_cache must be [NB, KVH, BS, D] of one dtype");
+  const int T = q.size(0), H = q.size(1), D = q.size(2);
+  const int KVH = k_cache.size(1), BS = k_cache.size(2);
+  TORCH_CHECK(D == 128 && k_cache.size(3) == 128, "attn_prefill_paged_split: head_dim must be 128");
+  TORCH_CHECK(KVH > 0 && H % KVH == 0, "attn_prefill_paged_split: H must be a multiple of KVH");
+  TORCH_CHECK(out.dim() == 3 && out.sizes() == q.sizes(),
+              "attn_prefill_paged_split: out must be [T, H, D]");
+  TORCH_CHECK(q.stride(0) >= (int64_t)H * D && q.stride(0) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "attn_prefill_paged_split: q token stride must cover H*D and keep rows 16-byte aligned");
+  auto ok = [](const torch::Tensor& t) {
+    return t.is_cuda() && t.is_contiguous() && t.scalar_type() == at::kInt;
+  };
+  TORCH_CHECK(ok(block_tables) && ok(cu_q) && ok(q_start) && ok(grp_seq) && ok(grp_qpos0) &&
+                  ok(grp_krange) && ok(grp_split) && ok(seq_nsplit) && ok(seq_ws_base),
+              "attn_prefill_paged_split: metadata must be contiguous int32 on GPU");
+  const int n_seq = q_start.numel();
+  TORCH_CHECK(n_seq >= 1 && cu_q.numel() == n_seq + 1, "cu_q must be [n_seq + 1]");
+  TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(0) == n_seq && block_tables.size(1) >= 1,
+              "block_tables must be [n_seq, max_blocks]");
+  const int n_groups = grp_seq.numel();
+  TORCH_CHECK(grp_qpos0.numel() == (int64_t)n_groups * 8, "grp_qpos0 must be [G*8]");
+  TORCH_CHECK(grp_krange.numel() == (int64_t)n_groups * 2, "grp_krange must be [G*2]");
+  TORCH_CHECK(grp_split.numel() == n_groups, "grp_split must be [G]");
+  TORCH_CHECK(seq_nsplit.numel() == n_seq && seq_ws_base.numel() == n_seq,
+              "seq_nsplit and seq_ws_base must be [n_seq]");
+  TORCH_CHECK(max_splits >= 2 && max_splits <= 64,
+              "attn_prefill_paged_split: max_splits must be 2..64");
+  TORCH_CHECK(ws_rows >= 1 && ws_rows <= (int64_t)T * max_splits,
+              "attn_prefill_paged_split: ws_rows must be 1..T*max_splits");
+  auto ws_ok = [&](const torch::Tensor& t, int64_t last) {
+    return t.is_cuda() && t.is_contiguous() && t.scalar_type() == at::kFloat && t.dim() == 3 &&
+           t.size(0) >= ws_rows && t.size(1) == H && t.size(2) == last &&
+           reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+  };
+  TORCH_CHECK(ws_ok(part_o, 128) && ws_ok(part_ml, 2),
+              "attn_prefill_paged_split: part_o / part_ml must be contiguous fp32 "
+              "[>= ws_rows, H, 128] / [>= ws_rows, H, 2]");
+  const int cache_fp8 = k_cache.scalar_type() == at::kFloat8_e4m3fn ? 1 : 0;
+  if (cache_fp8) {
+    TORCH_CHECK(k_scale.is_cuda() && v_scale.is_cuda() &&
+                    k_scale.numel() == k_cache.size(0) * KVH * BS && k_scale.is_contiguous() &&
+                    v_scale.is_contiguous() && k_scale.scalar_type() == at::kFloat &&
+                    v_scale.scalar_type() == at::kFloat && v_scale.numel() == k_scale.numel(),
+                "fp8 attn_prefill_paged_split requires [NB, KVH, BS] fp32 k_scale/v_scale");
+  } else {
+    TORCH_CHECK(k_scale.numel() == 0 && v_scale.numel() == 0,
+                "attn_prefill_paged_split: k_scale/v_scale go with fp8 caches only");
+  }
+  if (T == 0 || n_groups == 0) return;
+  launch_attn_prefill_paged_split(
+      bf(out), cbf(q), k_cache.data_ptr(), v_cache.data_ptr(),
+      cache_fp8 ? k_scale.data_ptr<float>() : nullptr,
+      cache_fp8 ? v_scale.data_ptr<float>() : nullptr,
+      block_tables.data_ptr<int>(), cu_q.data_ptr<int>(), q_start.data_ptr<int>(),
+      grp_seq.data_ptr<int>(), grp_qpos0.data_ptr<int>(), grp_krange.data_ptr<int>(),
+      grp_split.data_ptr<int>(), seq_nsplit.data_ptr<int>(), seq_ws_base.data_ptr<int>(),
+      part_o.data_ptr<float>(), part_ml.data_ptr<float>(), (int)ws_rows, (int)max_splits,
+      (float)scale, n_seq, T, H, KVH, (int)k_cache.size(0), BS, (int)block_tables.size(1),
+      (int)q.stride(0), n_groups, cache_fp8, cur_stream());
 }
 
 void sample(torch::Tensor tokens, torch::Tensor logprobs, torch::Tensor logits,
@@ -698,6 +780,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_paged_shared", &attn_decode_paged_shared);
   m.def("attn_prefill", &attn_prefill);
   m.def("attn_prefill_paged", &attn_prefill_paged);
+  m.def("attn_prefill_paged_split", &attn_prefill_paged_split);
   m.def("sample", &sample);
   m.def("sample_fsm", &sample_fsm);
   m.def("mfma_selftest", &mfma_selftest);

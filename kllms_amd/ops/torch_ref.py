@@ -260,6 +260,123 @@ def attn_prefill_paged(q, k_cache, v_cache, block_tables, cu_q, q_start, scale,
     return attn_decode_paged(q, k_cache, v_cache, bt, ctx, scale, k_scale, v_scale)
 
 
+def paged_prefill_split_partials(q, k_cache, v_cache, meta, scale, k_scale=None, v_scale=None,
+                                 p_bf16=False, kv_bf16=False, empty_init=False):
+    """The split plan of ``meta`` (ops.PagedPrefill with key splits) walked
+    group by group as the HIP kernel's grid does. Returns ``(out, m, l, o)``:
+    out [T, H, D] fp32 holds the rows of direct-epilogue groups (NaN
+    elsewhere); m, l [ws_rows, H] and o [ws_rows, H, D] are the partials, NaN
+    where no group wrote (``empty_init``: the empty partial instead), so that a
+    plan that leaves a slot uncovered shows in the result. ``p_bf16`` rounds
+    the probabilities entering P.V to bf16 (the normaliser keeps fp32);
+    ``kv_bf16`` rounds dequantised fp8 K/V to bf16, as the kernel's staging."""
+    T, H, D = q.shape
+    _, KVH, BS, _ = k_cache.shape
+    rep = H // KVH
+    cu = meta.cu_q.tolist()
+    starts = meta.q_start.tolist()
+    grp_seq = meta.grp_seq.tolist()
+    qpos = meta.grp_qpos0.tolist()
+    krange = meta.grp_krange.tolist()
+    split = meta.grp_split.tolist()
+    nsplit = meta.seq_nsplit.tolist()
+    base = meta.seq_ws_base.tolist()
+    f32 = dict(dtype=torch.float32, device=q.device)
+    out = torch.full((T, H, D), float("nan"), **f32)
+    W = meta.ws_rows
+    if empty_init:
+        pm = torch.full((W, H), float("-inf"), **f32)
+        pl, po = torch.zeros((W, H), **f32), torch.zeros((W, H, D), **f32)
+    else:
+        pm, pl = torch.full((W, H), float("nan"), **f32), torch.full((W, H), float("nan"), **f32)
+        po = torch.full((W, H, D), float("nan"), **f32)
+    for g, s in enumerate(grp_seq):
+        start, n = starts[s], cu[s + 1] - cu[s]
+        kbeg, kend = krange[2 * g], krange[2 * g + 1]
+        for r0 in qpos[8 * g: 8 * g + 8]:
+            if r0 < 0 or r0 >= n:
+                continue
+            r1 = min(r0 + 32, n)
+            k1 = min(kend, start + r1)               # the tile's causal bound
+            rows = torch.arange(r0, r1, device=q.device)
+            m = torch.full((r1 - r0, H), float("-inf"), **f32)
+            l = torch.zeros((r1 - r0, H), **f32)
+            o = torch.zeros((r1 - r0, H, D), **f32)
+            if k1 > kbeg:
+                j0, j1 = kbeg // BS, (k1 + BS - 1) // BS
+                blocks = meta.block_tables[s, j0:j1].long()
+                lo, hi = kbeg - j0 * BS, k1 - j0 * BS
+                nb = j1 - j0
+                kk = k_cache[blocks].permute(1, 0, 2, 3).reshape(KVH, nb * BS, D)[:, lo:hi].float()
+                vv = v_cache[blocks].permute(1, 0, 2, 3).reshape(KVH, nb * BS, D)[:, lo:hi].float()
+                if k_scale is not None:
+                    kk = kk * k_scale[blocks].permute(1, 0, 2).reshape(KVH, nb * BS)[:, lo:hi, None]
+                    vv = vv * v_scale[blocks].permute(1, 0, 2).reshape(KVH, nb * BS)[:, lo:hi, None]
+                    if kv_bf16:
+                        kk, vv = kk.bfloat16().float(), vv.bfloat16().float()
+                kk = kk.repeat_interleave(rep, dim=0)     # [H, keys, D]
+                vv = vv.repeat_interleave(rep, dim=0)
+                sc = torch.einsum("ihd,hjd->ihj", q[cu[s] + r0: cu[s] + r1].float(), kk) * scale
+                keys = torch.arange(kbeg, k1, device=q.device)
+                ok = keys[None, :] <= (start + rows)[:, None]          # [rows, keys]
+                sc = sc.masked_fill(~ok[:, None, :], float("-inf"))
+                m = sc.max(dim=-1).values
+                ref = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
+                p = torch.exp(sc - ref[..., None])                     # 0 where masked
+                l = p.sum(dim=-1)
+                if p_bf16:
+                    p = p.bfloat16().float()
+                o = torch.einsum("ihj,hjd->ihd", p, vv)
+            if split[g] < 0:
+                den = l[..., None]
+                out[cu[s] + r0: cu[s] + r1] = torch.where(den > 0, o / den.clamp_min(1e-38),
+                                                          torch.zeros_like(o))
+            else:
+                slots = base[s] + rows * nsplit[s] + split[g]
+                pm[slots], pl[slots], po[slots] = m, l, o
+    return out, pm, pl, po
+
+
+def paged_prefill_split_merge(out, pm, pl, po, meta):
+    """Merge of the partials into the rows of split sequences, in fp32 and in
+    split order: w_j = exp(m_j - max_j m_j), 0 for an empty partial (l_j = 0 or
+    m_j = -inf); out = sum_j w_j o_j / sum_j w_j l_j, zeros when that is 0."""
+    cu = meta.cu_q.tolist()
+    for s, (k, b) in enumerate(zip(meta.seq_nsplit.tolist(), meta.seq_ws_base.tolist())):
+        n = cu[s + 1] - cu[s]
+        if k < 2:
+            continue
+        H, D = po.shape[1:]
+        m = pm[b: b + n * k].view(n, k, H)
+        l = pl[b: b + n * k].view(n, k, H)
+        o = po[b: b + n * k].view(n, k, H, D)
+        empty = (l == 0) | (m == float("-inf"))
+        m_all = m.masked_fill(empty, float("-inf")).max(dim=1, keepdim=True).values
+        w = torch.where(empty, torch.zeros_like(m), torch.exp(m - m_all))
+        acc = torch.zeros((n, H, D), dtype=torch.float32, device=po.device)
+        den = torch.zeros((n, H), dtype=torch.float32, device=po.device)
+        for j in range(k):
+            wj = w[:, j]
+            acc = acc + torch.where(empty[:, j, :, None], torch.zeros_like(acc),
+                                    wj[..., None] * o[:, j])
+            den = den + torch.where(empty[:, j], torch.zeros_like(den), wj * l[:, j])
+        out[cu[s]: cu[s + 1]] = torch.where(den[..., None] > 0,
+                                            acc / den[..., None].clamp_min(1e-38),
+                                            torch.zeros_like(acc))
+    return out
+
+
+def attn_prefill_paged_split(q, k_cache, v_cache, meta, scale, k_scale=None, v_scale=None,
+                             p_bf16=False, kv_bf16=False) -> torch.Tensor:
+    """Paged prefill attention over a key-split plan: per-group partials, then
+    the merge, both in fp32. Every group and key range is taken from ``meta``
+    exactly as the HIP kernel takes it, so a plan that loses or repeats keys
+    gives a wrong (or NaN) result here too."""
+    out, pm, pl, po = paged_prefill_split_partials(q, k_cache, v_cache, meta, scale, k_scale,
+                                                   v_scale, p_bf16=p_bf16, kv_bf16=kv_bf16)
+    return paged_prefill_split_merge(out, pm, pl, po, meta).to(q.dtype)
+
+
 def _paged_partial(qb, k_cache, v_cache, blocks_row, k0, k1, scale, k_scale, v_scale):
     """Unnormalised softmax partial of one row's heads over keys [k0, k1) read
     through ``blocks_row``: (m [H], l [H], o [H, D]) in fp32."""
