@@ -20,31 +20,22 @@
 // through the block table of the tile's FIRST member only.
 //
 // Per workgroup: the chunk is processed in 2 rounds of 128 keys staged in
-// LDS (K XOR-swizzled, V transposed: the attn_prefill.hip layouts). The four
-// waves split the KEYS (32 per wave per round), never the rows: each wave
-// runs the swapped-QK^T flash loop of attn_prefill.hip over its keys for
-// both 32-row blocks, and the four (m, l, o) sets are merged through LDS at
-// the end.
-//
-// MFMA fragment maps (v_mfma_f32_32x32x16_bf16, verified on-device by the
-// mfma_selftest binding):
-//   A[i][k]: lane l holds i = l&31, k = (l>>5)*8 + j   (j = 0..7)
-//   B[k][j]: lane l holds j = l&31, k = (l>>5)*8 + jj
-//   C/D[i][j]: lane l holds j = l&31, i = (r&3) + 8*(r>>2) + 4*(l>>5)  (r = 0..15)
+// LDS (the attn_mfma.h layouts). The four waves split the KEYS (32 per wave
+// per round), never the rows: each wave runs the attn_mfma.h tile core over
+// its keys for both 32-row blocks — without defer-max, and unmasked: every
+// score is finite — and the four (m, l, o) sets are merged through LDS at the
+// end.
 
-#include "common.h"
-
-typedef __bf16 bf16x8_mfma __attribute__((ext_vector_type(8)));
+#include "attn_mfma.h"
 
 #define SP_THREADS 256
 #define SP_TILE_ROWS 64            // query rows per tile (2 MFMA row blocks)
 #define SP_ROUND_KEYS 128          // keys staged per barrier round (32 per wave)
-#define SP_K_ROW_BYTES 256         // 128 bf16
 #define SP_VT_ROW 136              // shorts: 128 keys + 8 pad (conflict-free b128 reads)
 #define SP_O_STRIDE 132            // floats per merged-o row (16B-aligned rows)
 #define SP_PART_STRIDE 130
 
-#define SP_STAGE_BYTES (SP_ROUND_KEYS * SP_K_ROW_BYTES + 128 * SP_VT_ROW * 2)   // 67584
+#define SP_STAGE_BYTES (SP_ROUND_KEYS * ATTN_K_ROW_BYTES + 128 * SP_VT_ROW * 2)   // 67584
 #define SP_MERGE_BYTES (4 * 32 * SP_O_STRIDE * 4)                              // 67584
 #define SP_LDS_BYTES ((SP_STAGE_BYTES > SP_MERGE_BYTES ? SP_STAGE_BYTES : SP_MERGE_BYTES) + 4 * 32 * 2 * 4)
 
@@ -86,7 +77,7 @@ __global__ __launch_bounds__(SP_THREADS, 2) void attn_decode_shared_t(
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* k_lds = smem;                                                    // [128][256B] swizzled
-  short* vt_lds = reinterpret_cast<short*>(smem + SP_ROUND_KEYS * SP_K_ROW_BYTES);  // [128][136]
+  short* vt_lds = reinterpret_cast<short*>(smem + SP_ROUND_KEYS * ATTN_K_ROW_BYTES);  // [128][136]
   float* o_lds = reinterpret_cast<float*>(smem);                         // [4][32][132] (epilogue)
   float* ml_lds = reinterpret_cast<float*>(
       smem + (SP_STAGE_BYTES > SP_MERGE_BYTES ? SP_STAGE_BYTES : SP_MERGE_BYTES));  // [4][32][2]
@@ -111,6 +102,7 @@ __global__ __launch_bounds__(SP_THREADS, 2) void attn_decode_shared_t(
   const int* bt = block_tables + (int64_t)b0 * max_blocks;
   const int key_base = chunk * ATTN_DECODE_CHUNK;
 
+#pragma unroll 1   // the two rounds stay a loop: one copy of the round body
   for (int round = 0; round < ATTN_DECODE_CHUNK / SP_ROUND_KEYS; ++round) {
     // ---- stage K (swizzled) + V^T: 128 keys x 8 slivers of 16 dims ---------
 #pragma unroll
@@ -128,27 +120,14 @@ __global__ __launch_bounds__(SP_THREADS, 2) void attn_decode_shared_t(
         const u8x16_vec v8 = *reinterpret_cast<const u8x16_vec*>(v_cache + row * 128 + piece * 16);
         const float ks = k_scale[row];
         const float vs = v_scale[row];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          ka[j] = f32_to_bf16(fp8_to_f32(k8[j]) * ks);
-          kb[j] = f32_to_bf16(fp8_to_f32(k8[8 + j]) * ks);
-          va[j] = f32_to_bf16(fp8_to_f32(v8[j]) * vs);
-          vb[j] = f32_to_bf16(fp8_to_f32(v8[8 + j]) * vs);
-        }
+        dequant_sliver(k8, ks, v8, vs, ka, kb, va, vb);
       } else {
         const bf16x8_vec* kp = reinterpret_cast<const bf16x8_vec*>(k_cache + row * 256) + piece * 2;
         const bf16x8_vec* vp = reinterpret_cast<const bf16x8_vec*>(v_cache + row * 256) + piece * 2;
         ka = kp[0]; kb = kp[1];
         va = vp[0]; vb = vp[1];
       }
-      const int swz = (key & 15) << 4;
-      *reinterpret_cast<bf16x8_vec*>(k_lds + key * SP_K_ROW_BYTES + ((piece * 32) ^ swz)) = ka;
-      *reinterpret_cast<bf16x8_vec*>(k_lds + key * SP_K_ROW_BYTES + ((piece * 32 + 16) ^ swz)) = kb;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        vt_lds[(piece * 16 + j) * SP_VT_ROW + key] = va[j];
-        vt_lds[(piece * 16 + 8 + j) * SP_VT_ROW + key] = vb[j];
-      }
+      stage_sliver<SP_VT_ROW>(k_lds, vt_lds, key, piece, ka, kb, va, vb);
     }
     __syncthreads();
 
@@ -157,85 +136,21 @@ __global__ __launch_bounds__(SP_THREADS, 2) void attn_decode_shared_t(
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb) {
       if (rb < nrb) {
-        // QK^T (swapped): S[key][qrow] over 8 d-slices; Q re-read per round
-        // (L2-resident, 2 rounds) so it does not pin 64 VGPRs
-        f32x16 s_acc = {};
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
+        // Q re-read per round (L2-resident, 2 rounds) so it does not pin 64
+        // VGPRs
+        const f32x16 s_acc = qk_subtile(k_lds, krow, half, [&](int s) {
           bf16x8_mfma qf = {};
           if (q_ptr[rb] != nullptr)
             qf = *reinterpret_cast<const bf16x8_mfma*>((const short*)q_ptr[rb] + s * 16 + half * 8);
-          const int byte_off = (s * 2 + half) * 16;
-          const bf16x8_mfma a_frag = *reinterpret_cast<const bf16x8_mfma*>(
-              k_lds + krow * SP_K_ROW_BYTES + (byte_off ^ ((krow & 15) << 4)));
-          s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_frag, qf, s_acc, 0, 0, 0);
-        }
+          return qf;
+        });
 
-        // online softmax, row = lane-local (the two halves hold 16 keys each)
         float sv[16];
-        float tmax = -INFINITY;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          sv[r] = s_acc[r] * scale;
-          tmax = fmaxf(tmax, sv[r]);
-        }
-        {
-          auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(tmax), __float_as_uint(tmax), false, false);
-          tmax = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-        }
-        const float m_new = fmaxf(m_run[rb], tmax);
-        const float alpha = (m_run[rb] == -INFINITY) ? 0.0f : __expf(m_run[rb] - m_new);
-        m_run[rb] = m_new;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) o_acc[rb][dt][r] *= alpha;
+        for (int r = 0; r < 16; ++r) sv[r] = s_acc[r] * scale;
 
-        float p[16];
-        float psum = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          p[r] = __expf(sv[r] - m_new);
-          psum += p[r];
-        }
-        l_run[rb] = l_run[rb] * alpha + psum;
-
-        // repack P -> bf16 B-fragments (half swaps, as attn_prefill.hip)
-        uint32_t packs[8];
-#pragma unroll
-        for (int pr = 0; pr < 8; ++pr) {
-          const short lo = f32_to_bf16(p[2 * pr]);
-          const short hi = f32_to_bf16(p[2 * pr + 1]);
-          packs[pr] = ((uint32_t)(uint16_t)hi << 16) | (uint16_t)lo;
-        }
-        uint32_t bfrag[2][4];
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt) {
-          auto r0 = __builtin_amdgcn_permlane32_swap(packs[4 * kt + 0], packs[4 * kt + 2], false, false);
-          auto r1 = __builtin_amdgcn_permlane32_swap(packs[4 * kt + 1], packs[4 * kt + 3], false, false);
-          bfrag[kt][0] = r0[0];
-          bfrag[kt][1] = r1[0];
-          bfrag[kt][2] = r0[1];
-          bfrag[kt][3] = r1[1];
-        }
-
-        // PV: O^T += V^T x P over 4 d-tiles
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-          const int d_row = dt * 32 + col;
-#pragma unroll
-          for (int kt = 0; kt < 2; ++kt) {
-            const bf16x8_mfma vfrag = *reinterpret_cast<const bf16x8_mfma*>(
-                vt_lds + d_row * SP_VT_ROW + wave * 32 + kt * 16 + half * 8);
-            bf16x8_mfma pfrag;
-            {
-              uint32_t* pf = reinterpret_cast<uint32_t*>(&pfrag);
-#pragma unroll
-              for (int w = 0; w < 4; ++w) pf[w] = bfrag[kt][w];
-            }
-            o_acc[rb][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfrag, pfrag, o_acc[rb][dt], 0, 0, 0);
-          }
-        }
+        softmax_pv_subtile<SP_VT_ROW, false, false>(sv, m_run[rb], l_run[rb], o_acc[rb], vt_lds,
+                                                    wave * 32, col, half);
       }
     }
     __syncthreads();   // staging buffers are rewritten next round / by the merge
@@ -245,23 +160,12 @@ __global__ __launch_bounds__(SP_THREADS, 2) void attn_decode_shared_t(
 #pragma unroll
   for (int rb = 0; rb < 2; ++rb) {
     if (rb < nrb) {
-      float l_row;
-      {
-        auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run[rb]), __float_as_uint(l_run[rb]), false, false);
-        l_row = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-      }
+      const float l_row = half_merge_sum(l_run[rb]);
       float* ow = o_lds + ((wave * 32 + col) * SP_O_STRIDE);
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
+      for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
-        for (int g2 = 0; g2 < 4; ++g2) {   // regs 4*g2..+3 = 4 consecutive d
-          const int d0 = dt * 32 + 8 * g2 + 4 * half;
-          f32x4 v4;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v4[j] = o_acc[rb][dt][4 * g2 + j];
-          *reinterpret_cast<f32x4*>(ow + d0) = v4;
-        }
-      }
+        for (int g2 = 0; g2 < 4; ++g2) store_o_f32(ow, o_acc[rb][dt], dt, g2, half);
       if (half == 0) {
         ml_lds[(wave * 32 + col) * 2] = m_run[rb];
         ml_lds[(wave * 32 + col) * 2 + 1] = l_row;

@@ -1,6 +1,6 @@
 // Paged ("append" / "extend") causal prefill attention for gfx950 — the flash
-// MFMA loop of attn_prefill.hip with its K/V tiles gathered from the paged
-// cache as attn_decode_shared.hip does.
+// MFMA tile core of attn_mfma.h with its K/V tiles gathered from the paged
+// cache.
 //
 // Sequence s has q_start[s] keys already in the cache and q_len[s] =
 // cu_q[s+1] - cu_q[s] new tokens packed at rows cu_q[s].. of q/out. Row i of
@@ -10,7 +10,7 @@
 // are no k / v arguments. bf16 or e4m3 caches; e4m3 rows are dequantised as
 // bf16(fp8 * row_scale) on the way into LDS.
 //
-// Structure (see attn_prefill.hip for the fragment maps and the LDS layouts):
+// Structure (see attn_mfma.h for the fragment maps and the LDS layouts):
 //   - an 8-wave workgroup serves up to 8 32-row q-tiles of ONE (sequence,
 //     q-head); the waves share the K/V staging. How many tiles the host packs
 //     per workgroup is its choice (grp_qpos0 = -1 marks an idle wave, which
@@ -19,8 +19,6 @@
 //   - 64 keys per barrier round; the NEXT round's global loads are issued
 //     before this round's MFMA work and written to LDS after it, so the
 //     gather latency overlaps the compute;
-//   - swapped QK^T, lane-local online softmax with defer-max, P repacked to
-//     bf16 B-fragments, O^T = V^T x P;
 //   - a 32-key sub-tile lying wholly at or below the wave's first row limit
 //     (all prefix keys, and the new keys of earlier tiles) takes no mask; only
 //     sub-tiles overlapping the wave's own diagonal are masked.
@@ -40,20 +38,14 @@
 // direct epilogue, so one launch serves split and unsplit sequences. kbeg,
 // kend, the split index and the slot are clamped like the rest.
 
-#include "common.h"
+#include "attn_mfma.h"
 
-typedef __bf16 bf16x8_mfma __attribute__((ext_vector_type(8)));
 typedef float pp_f32x2 __attribute__((ext_vector_type(2)));
 
 #define PP_QBLK 32
 #define PP_KVBLK 64                // staged keys per barrier round (2 MFMA sub-tiles)
 #define PP_NWAVES 8
-#define PP_K_ROW_BYTES 256         // 128 bf16
 #define PP_VT_ROW 72               // shorts: 64 keys + 8 pad (conflict-free b128 reads)
-
-__device__ __forceinline__ int pp_acc_row(int r, int half) {
-  return (r & 3) + 8 * (r >> 2) + 4 * half;   // C/D row map
-}
 
 // one thread's share of a staged round: a 16-dim sliver of one key's K and V
 template <bool FP8> struct PPRegs;
@@ -114,10 +106,10 @@ __global__ __launch_bounds__(64 * PP_NWAVES) void attn_prefill_paged_t(
   const int my_limit = start + my_qpos;          // last key this row sees
   const int kv_cap = (int)min((int64_t)max_blocks * block_size, (int64_t)0x7fffffff);
 
-  __shared__ __attribute__((aligned(16))) char smem[PP_KVBLK * PP_K_ROW_BYTES +
+  __shared__ __attribute__((aligned(16))) char smem[PP_KVBLK * ATTN_K_ROW_BYTES +
                                                     128 * PP_VT_ROW * 2];
   char* k_lds = smem;                                   // [64][256B], XOR-swizzled
-  short* vt_lds = reinterpret_cast<short*>(smem + PP_KVBLK * PP_K_ROW_BYTES);  // [128][72]
+  short* vt_lds = reinterpret_cast<short*>(smem + PP_KVBLK * ATTN_K_ROW_BYTES);  // [128][72]
 
   // ---- Q fragments (B-operand): 8 d-slices of 16 --------------------------
   bf16x8_mfma q_frag[8];
@@ -186,24 +178,11 @@ __global__ __launch_bounds__(64 * PP_NWAVES) void attn_prefill_paged_t(
   auto store_round = [&](const PPRegs<FP8>& r) {
     bf16x8_vec ka, kb, va, vb;
     if constexpr (FP8) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        ka[j] = f32_to_bf16(fp8_to_f32(r.k8[j]) * r.ks);
-        kb[j] = f32_to_bf16(fp8_to_f32(r.k8[8 + j]) * r.ks);
-        va[j] = f32_to_bf16(fp8_to_f32(r.v8[j]) * r.vs);
-        vb[j] = f32_to_bf16(fp8_to_f32(r.v8[8 + j]) * r.vs);
-      }
+      dequant_sliver(r.k8, r.ks, r.v8, r.vs, ka, kb, va, vb);
     } else {
       ka = r.ka; kb = r.kb; va = r.va; vb = r.vb;
     }
-    const int swz = (st_key & 15) << 4;
-    *reinterpret_cast<bf16x8_vec*>(k_lds + st_key * PP_K_ROW_BYTES + ((st_piece * 32) ^ swz)) = ka;
-    *reinterpret_cast<bf16x8_vec*>(k_lds + st_key * PP_K_ROW_BYTES + ((st_piece * 32 + 16) ^ swz)) = kb;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      vt_lds[(st_piece * 16 + j) * PP_VT_ROW + st_key] = va[j];
-      vt_lds[(st_piece * 16 + 8 + j) * PP_VT_ROW + st_key] = vb[j];
-    }
+    stage_sliver<PP_VT_ROW>(k_lds, vt_lds, st_key, st_piece, ka, kb, va, vb);
   };
 
   PPRegs<FP8> regs;
@@ -221,16 +200,8 @@ __global__ __launch_bounds__(64 * PP_NWAVES) void attn_prefill_paged_t(
     const int kt0 = kt00 + sub * 32;
     const int nkeys = min(32, nkeys_blk - sub * 32);
     if (active && kt0 < kv_end_me && nkeys > 0) {
-      // ---- QK^T: S[key][qrow] over 8 d-slices -----------------------------
-      f32x16 s_acc = {};
-#pragma unroll
-      for (int s = 0; s < 8; ++s) {
-        const int byte_off = (s * 2 + half) * 16;
-        const int krow = col + sub * 32;
-        bf16x8_mfma a_frag = *reinterpret_cast<const bf16x8_mfma*>(
-            k_lds + krow * PP_K_ROW_BYTES + (byte_off ^ ((krow & 15) << 4)));
-        s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_frag, q_frag[s], s_acc, 0, 0, 0);
-      }
+      const f32x16 s_acc = qk_subtile(k_lds, col + sub * 32, half,
+                                      [&](int s) { return q_frag[s]; });
 
       // ---- scale (+ causal mask on the diagonal sub-tiles only) ------------
       // every key of a sub-tile ending at or before the wave's FIRST row limit
@@ -242,97 +213,23 @@ __global__ __launch_bounds__(64 * PP_NWAVES) void attn_prefill_paged_t(
       } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int kr = pp_acc_row(r, half);
+          const int kr = acc_row(r, half);
           const bool ok = (kt0 + kr <= my_limit) && (kr < nkeys);
           sv[r] = ok ? s_acc[r] * scale : -INFINITY;
         }
       }
 
-      // ---- online softmax (row = lane-local) -------------------------------
-      float tmax = sv[0];
-#pragma unroll
-      for (int r = 1; r < 16; ++r) tmax = fmaxf(tmax, sv[r]);
-      {
-        auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(tmax), __float_as_uint(tmax), false, false);
-        tmax = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-      }
-      // defer-max: keep the old running max while the tile max grew < THR (P
-      // then bounded by e^THR); decided BEFORE this tile's P is exponentiated
-      const float DEFER_THR = 8.0f;
-      float m_new, alpha;
-      // first visible key: m_run=-inf fails this. A row that has seen no key
-      // yet and sees none here (a split range above its causal limit) has
-      // tmax = m_run = -inf, keeps m_run and adds p = 0.
-      if (tmax <= m_run + DEFER_THR) {
-        m_new = m_run;
-        alpha = 1.0f;
-      } else {
-        m_new = fmaxf(m_run, tmax);
-        alpha = (m_run == -INFINITY) ? 0.0f : __expf(m_run - m_new);
-      }
-      m_run = m_new;
-      if (__builtin_amdgcn_ballot_w64(alpha != 1.0f)) {
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) o_acc[dt][r] *= alpha;
-      }
-
-      float p[16];
-      float psum = 0.0f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        p[r] = (sv[r] == -INFINITY) ? 0.0f : __expf(sv[r] - m_new);
-        psum += p[r];
-      }
-      l_run = l_run * alpha + psum;
-
-      // ---- repack P -> bf16 B-fragments (half swaps) -----------------------
-      uint32_t packs[8];
-#pragma unroll
-      for (int pr = 0; pr < 8; ++pr) {
-        const short lo = f32_to_bf16(p[2 * pr]);
-        const short hi = f32_to_bf16(p[2 * pr + 1]);
-        packs[pr] = ((uint32_t)(uint16_t)hi << 16) | (uint16_t)lo;
-      }
-      uint32_t bfrag[2][4];
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt) {
-        auto r0 = __builtin_amdgcn_permlane32_swap(packs[4 * kt + 0], packs[4 * kt + 2], false, false);
-        auto r1 = __builtin_amdgcn_permlane32_swap(packs[4 * kt + 1], packs[4 * kt + 3], false, false);
-        bfrag[kt][0] = r0[0];
-        bfrag[kt][1] = r1[0];
-        bfrag[kt][2] = r0[1];
-        bfrag[kt][3] = r1[1];
-      }
-
-      // ---- PV: O^T += V^T x P ----------------------------------------------
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        const int d_row = dt * 32 + col;
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt) {
-          bf16x8_mfma vfrag = *reinterpret_cast<const bf16x8_mfma*>(
-              vt_lds + d_row * PP_VT_ROW + sub * 32 + kt * 16 + half * 8);
-          bf16x8_mfma pfrag;
-          {
-            uint32_t* pf = reinterpret_cast<uint32_t*>(&pfrag);
-#pragma unroll
-            for (int w = 0; w < 4; ++w) pf[w] = bfrag[kt][w];
-          }
-          o_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfrag, pfrag, o_acc[dt], 0, 0, 0);
-        }
-      }
+      // a row that has seen no key yet and sees none here (a split range above
+      // its causal limit) keeps m_run = -inf and adds p = 0
+      softmax_pv_subtile<PP_VT_ROW, true, true>(sv, m_run, l_run, o_acc, vt_lds, sub * 32,
+                                                col, half);
     }
     }  // sub
     __syncthreads();   // the staging buffers are rewritten next round
   }
 
   // ---- epilogue: merge half-sums, normalize, write O ----------------------
-  {
-    auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
-    l_run = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-  }
+  l_run = half_merge_sum(l_run);
   if constexpr (SPLIT) {
     const int split = sp.grp_split[grp];            // workgroup-uniform
     if (split >= 0) {
@@ -346,16 +243,9 @@ __global__ __launch_bounds__(64 * PP_NWAVES) void attn_prefill_paged_t(
         const int64_t cell = slot * num_q_heads + h;
         float* po = sp.part_o + cell * 128;
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
+        for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
-          for (int g2 = 0; g2 < 4; ++g2) {
-            const int d0 = dt * 32 + 8 * g2 + 4 * half;
-            f32x4 v4;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v4[j] = o_acc[dt][4 * g2 + j];
-            *reinterpret_cast<f32x4*>(po + d0) = v4;
-          }
-        }
+          for (int g2 = 0; g2 < 4; ++g2) store_o_f32(po, o_acc[dt], dt, g2, half);
         if (half == 0) {
           pp_f32x2 ml;
           ml[0] = m_run;
@@ -370,19 +260,9 @@ __global__ __launch_bounds__(64 * PP_NWAVES) void attn_prefill_paged_t(
     const float inv_l = (l_run > 0.0f) ? 1.0f / l_run : 0.0f;
     bf16_t* op = out + (((int64_t)(row0 + my_qpos)) * num_q_heads + h) * 128;
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
+    for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
-      for (int g2 = 0; g2 < 4; ++g2) {   // regs 4*g2..+3 = d consecutive
-        const int d0 = dt * 32 + 8 * g2 + 4 * half;
-        uint64_t word = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float val = o_acc[dt][4 * g2 + j] * inv_l;
-          word |= ((uint64_t)(uint16_t)f32_to_bf16(val)) << (16 * j);
-        }
-        *reinterpret_cast<uint64_t*>((short*)op + d0) = word;
-      }
-    }
+      for (int g2 = 0; g2 < 4; ++g2) store_o_bf16(op, o_acc[dt], inv_l, dt, g2, half);
   }
 }
 
@@ -442,6 +322,23 @@ __global__ __launch_bounds__(32 * PP_RED_HEADS) void attn_prefill_paged_reduce(
   *reinterpret_cast<uint64_t*>((short*)(out + ((int64_t)t * num_q_heads + h) * 128) + d0) = word;
 }
 
+// the one launch of attn_prefill_paged_t, behind both entry points
+template <bool FP8, typename SP>
+static void pp_launch(
+    bf16_t* out, const bf16_t* q, const void* k_cache, const void* v_cache,
+    const float* k_scale, const float* v_scale, const int* block_tables,
+    const int* cu_q, const int* q_start, const int* grp_seq, const int* grp_qpos0,
+    float scale, int n_seq, int total_rows, int num_q_heads, int num_kv_heads,
+    int num_blocks, int block_size, int max_blocks, int q_tstride, int n_groups,
+    SP sp, hipStream_t stream) {
+  hipLaunchKernelGGL((attn_prefill_paged_t<FP8, SP>), dim3(n_groups, num_q_heads),
+                     dim3(64 * PP_NWAVES), 0, stream,
+                     out, q, (const char*)k_cache, (const char*)v_cache, k_scale, v_scale,
+                     block_tables, cu_q, q_start, grp_seq, grp_qpos0, scale, n_seq,
+                     total_rows, num_q_heads, num_kv_heads, num_blocks, block_size,
+                     max_blocks, q_tstride, sp);
+}
+
 // host-side launcher; an empty grid is the caller's to skip
 extern "C" void launch_attn_prefill_paged(
     bf16_t* out, const bf16_t* q, const void* k_cache, const void* v_cache,
@@ -451,20 +348,10 @@ extern "C" void launch_attn_prefill_paged(
     int num_blocks, int block_size, int max_blocks, int q_tstride, int n_groups,
     int cache_fp8, hipStream_t stream) {
   if (n_groups <= 0 || n_seq <= 0 || total_rows <= 0) return;
-  const dim3 grid(n_groups, num_q_heads);
-  if (cache_fp8) {
-    hipLaunchKernelGGL((attn_prefill_paged_t<true>), grid, dim3(64 * PP_NWAVES), 0, stream,
-                       out, q, (const char*)k_cache, (const char*)v_cache, k_scale, v_scale,
-                       block_tables, cu_q, q_start, grp_seq, grp_qpos0, scale, n_seq,
-                       total_rows, num_q_heads, num_kv_heads, num_blocks, block_size,
-                       max_blocks, q_tstride, PPNoSplit{});
-  } else {
-    hipLaunchKernelGGL((attn_prefill_paged_t<false>), grid, dim3(64 * PP_NWAVES), 0, stream,
-                       out, q, (const char*)k_cache, (const char*)v_cache, k_scale, v_scale,
-                       block_tables, cu_q, q_start, grp_seq, grp_qpos0, scale, n_seq,
-                       total_rows, num_q_heads, num_kv_heads, num_blocks, block_size,
-                       max_blocks, q_tstride, PPNoSplit{});
-  }
+  (cache_fp8 ? pp_launch<true, PPNoSplit> : pp_launch<false, PPNoSplit>)(
+      out, q, k_cache, v_cache, k_scale, v_scale, block_tables, cu_q, q_start, grp_seq,
+      grp_qpos0, scale, n_seq, total_rows, num_q_heads, num_kv_heads, num_blocks, block_size,
+      max_blocks, q_tstride, n_groups, PPNoSplit{}, stream);
 }
 
 // split launch + merge; the caller has checked the workspace against ws_rows
@@ -480,20 +367,10 @@ extern "C" void launch_attn_prefill_paged_split(
   if (n_groups <= 0 || n_seq <= 0 || total_rows <= 0 || ws_rows <= 0) return;
   const PPSplit sp{grp_krange, grp_split, seq_nsplit, seq_ws_base, part_o, part_ml,
                    ws_rows, max_splits};
-  const dim3 grid(n_groups, num_q_heads);
-  if (cache_fp8) {
-    hipLaunchKernelGGL((attn_prefill_paged_t<true, PPSplit>), grid, dim3(64 * PP_NWAVES), 0, stream,
-                       out, q, (const char*)k_cache, (const char*)v_cache, k_scale, v_scale,
-                       block_tables, cu_q, q_start, grp_seq, grp_qpos0, scale, n_seq,
-                       total_rows, num_q_heads, num_kv_heads, num_blocks, block_size,
-                       max_blocks, q_tstride, sp);
-  } else {
-    hipLaunchKernelGGL((attn_prefill_paged_t<false, PPSplit>), grid, dim3(64 * PP_NWAVES), 0, stream,
-                       out, q, (const char*)k_cache, (const char*)v_cache, k_scale, v_scale,
-                       block_tables, cu_q, q_start, grp_seq, grp_qpos0, scale, n_seq,
-                       total_rows, num_q_heads, num_kv_heads, num_blocks, block_size,
-                       max_blocks, q_tstride, sp);
-  }
+  (cache_fp8 ? pp_launch<true, PPSplit> : pp_launch<false, PPSplit>)(
+      out, q, k_cache, v_cache, k_scale, v_scale, block_tables, cu_q, q_start, grp_seq,
+      grp_qpos0, scale, n_seq, total_rows, num_q_heads, num_kv_heads, num_blocks, block_size,
+      max_blocks, q_tstride, n_groups, sp, stream);
   const dim3 rgrid(total_rows, (num_q_heads + PP_RED_HEADS - 1) / PP_RED_HEADS);
   hipLaunchKernelGGL(attn_prefill_paged_reduce, rgrid, dim3(32 * PP_RED_HEADS), 0, stream,
                      out, part_o, part_ml, cu_q, seq_nsplit, seq_ws_base, n_seq, total_rows,

@@ -1,6 +1,8 @@
 // PyTorch bindings for the kllms_amd gfx950 kernels (kllms_amd._C).
 // Thin launch shims: shape/dtype checks, grid math, current-HIP-stream launch.
 
+#include <algorithm>
+
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
@@ -299,33 +301,36 @@ void attn_prefill(torch::Tensor out, torch::Tensor q, torch::Tensor k, torch::Te
                      (int)q.stride(0), (int)k.stride(0));
 }
 
-// Paged (append / extend) prefill attention: new tokens packed at rows
-// cu_q[s]..cu_q[s+1] attend causally to the q_start[s] keys already cached
-// plus themselves, all read through block_tables[s] (one row per sequence).
-// grp_seq [G] / grp_qpos0 [G*8] are the per-workgroup q-tiles of
-// ops.build_paged_prefill, which also checks q_start + q_len against the
-// table width on the host.
-void attn_prefill_paged(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
-                        torch::Tensor v_cache, torch::Tensor block_tables, torch::Tensor cu_q,
-                        torch::Tensor q_start, torch::Tensor grp_seq, torch::Tensor grp_qpos0,
-                        double scale, torch::Tensor k_scale, torch::Tensor v_scale) {
+// The argument checks attn_prefill_paged and attn_prefill_paged_split share;
+// `op` names the binding in the messages and `extra_meta` is the int32
+// metadata only that binding takes.
+struct PagedPrefillDims { int T, H, KVH, BS, n_seq, n_groups, cache_fp8; };
+
+static PagedPrefillDims check_paged_prefill(
+    const char* op, const torch::Tensor& out, const torch::Tensor& q,
+    const torch::Tensor& k_cache, const torch::Tensor& v_cache,
+    const torch::Tensor& block_tables, const torch::Tensor& cu_q, const torch::Tensor& q_start,
+    const torch::Tensor& grp_seq, const torch::Tensor& grp_qpos0,
+    const torch::Tensor& k_scale, const torch::Tensor& v_scale,
+    std::initializer_list<torch::Tensor> extra_meta = {}) {
   CHECK_BF16_CONTIG(out); CHECK_BF16_ROWS(q); CHECK_KV_CACHE(k_cache); CHECK_KV_CACHE(v_cache);
   TORCH_CHECK(k_cache.dim() == 4 && v_cache.sizes() == k_cache.sizes() &&
                   v_cache.scalar_type() == k_cache.scalar_type(),
-              "attn_prefill_paged: k_cache/v_cache must be [NB, KVH, BS, D] of one dtype");
+              op, ": k_cache/v_cache must be [NB, KVH, BS, D] of one dtype");
   const int T = q.size(0), H = q.size(1), D = q.size(2);
   const int KVH = k_cache.size(1), BS = k_cache.size(2);
-  TORCH_CHECK(D == 128 && k_cache.size(3) == 128, "attn_prefill_paged: head_dim must be 128");
-  TORCH_CHECK(KVH > 0 && H % KVH == 0, "attn_prefill_paged: H must be a multiple of KVH");
-  TORCH_CHECK(out.dim() == 3 && out.sizes() == q.sizes(), "attn_prefill_paged: out must be [T, H, D]");
+  TORCH_CHECK(D == 128 && k_cache.size(3) == 128, op, ": head_dim must be 128");
+  TORCH_CHECK(KVH > 0 && H % KVH == 0, op, ": H must be a multiple of KVH");
+  TORCH_CHECK(out.dim() == 3 && out.sizes() == q.sizes(), op, ": out must be [T, H, D]");
   TORCH_CHECK(q.stride(0) >= (int64_t)H * D && q.stride(0) % 8 == 0 &&
                   reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
-              "attn_prefill_paged: q token stride must cover H*D and keep rows 16-byte aligned");
+              op, ": q token stride must cover H*D and keep rows 16-byte aligned");
   auto ok = [](const torch::Tensor& t) {
     return t.is_cuda() && t.is_contiguous() && t.scalar_type() == at::kInt;
   };
-  TORCH_CHECK(ok(block_tables) && ok(cu_q) && ok(q_start) && ok(grp_seq) && ok(grp_qpos0),
-              "attn_prefill_paged: metadata must be contiguous int32 on GPU");
+  TORCH_CHECK(ok(block_tables) && ok(cu_q) && ok(q_start) && ok(grp_seq) && ok(grp_qpos0) &&
+                  std::all_of(extra_meta.begin(), extra_meta.end(), ok),
+              op, ": metadata must be contiguous int32 on GPU");
   const int n_seq = q_start.numel();
   TORCH_CHECK(n_seq >= 1 && cu_q.numel() == n_seq + 1, "cu_q must be [n_seq + 1]");
   TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(0) == n_seq && block_tables.size(1) >= 1,
@@ -338,20 +343,36 @@ void attn_prefill_paged(torch::Tensor out, torch::Tensor q, torch::Tensor k_cach
                     k_scale.numel() == k_cache.size(0) * KVH * BS && k_scale.is_contiguous() &&
                     v_scale.is_contiguous() && k_scale.scalar_type() == at::kFloat &&
                     v_scale.scalar_type() == at::kFloat && v_scale.numel() == k_scale.numel(),
-                "fp8 attn_prefill_paged requires [NB, KVH, BS] fp32 k_scale/v_scale");
+                "fp8 ", op, " requires [NB, KVH, BS] fp32 k_scale/v_scale");
   } else {
     TORCH_CHECK(k_scale.numel() == 0 && v_scale.numel() == 0,
-                "attn_prefill_paged: k_scale/v_scale go with fp8 caches only");
+                op, ": k_scale/v_scale go with fp8 caches only");
   }
-  if (T == 0 || n_groups == 0) return;
+  return {T, H, KVH, BS, n_seq, n_groups, cache_fp8};
+}
+
+// Paged (append / extend) prefill attention: new tokens packed at rows
+// cu_q[s]..cu_q[s+1] attend causally to the q_start[s] keys already cached
+// plus themselves, all read through block_tables[s] (one row per sequence).
+// grp_seq [G] / grp_qpos0 [G*8] are the per-workgroup q-tiles of
+// ops.build_paged_prefill, which also checks q_start + q_len against the
+// table width on the host.
+void attn_prefill_paged(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
+                        torch::Tensor v_cache, torch::Tensor block_tables, torch::Tensor cu_q,
+                        torch::Tensor q_start, torch::Tensor grp_seq, torch::Tensor grp_qpos0,
+                        double scale, torch::Tensor k_scale, torch::Tensor v_scale) {
+  const PagedPrefillDims d = check_paged_prefill(
+      "attn_prefill_paged", out, q, k_cache, v_cache, block_tables, cu_q, q_start, grp_seq,
+      grp_qpos0, k_scale, v_scale);
+  if (d.T == 0 || d.n_groups == 0) return;
   launch_attn_prefill_paged(
       bf(out), cbf(q), k_cache.data_ptr(), v_cache.data_ptr(),
-      cache_fp8 ? k_scale.data_ptr<float>() : nullptr,
-      cache_fp8 ? v_scale.data_ptr<float>() : nullptr,
+      d.cache_fp8 ? k_scale.data_ptr<float>() : nullptr,
+      d.cache_fp8 ? v_scale.data_ptr<float>() : nullptr,
       block_tables.data_ptr<int>(), cu_q.data_ptr<int>(), q_start.data_ptr<int>(),
-      grp_seq.data_ptr<int>(), grp_qpos0.data_ptr<int>(), (float)scale, n_seq, T, H, KVH,
-      (int)k_cache.size(0), BS, (int)block_tables.size(1), (int)q.stride(0), n_groups,
-      cache_fp8, cur_stream());
+      grp_seq.data_ptr<int>(), grp_qpos0.data_ptr<int>(), (float)scale, d.n_seq, d.T, d.H,
+      d.KVH, (int)k_cache.size(0), d.BS, (int)block_tables.size(1), (int)q.stride(0),
+      d.n_groups, d.cache_fp8, cur_stream());
 }
 
 // attn_prefill_paged with the keys of some sequences split across workgroups
@@ -370,69 +391,36 @@ void attn_prefill_paged_split(torch::Tensor out, torch::Tensor q, torch::Tensor 
                               torch::Tensor seq_ws_base, torch::Tensor part_o,
                               torch::Tensor part_ml, int64_t ws_rows, int64_t max_splits,
                               double scale, torch::Tensor k_scale, torch::Tensor v_scale) {
-  CHECK_BF16_CONTIG(out); CHECK_BF16_ROWS(q); CHECK_KV_CACHE(k_cache); CHECK_KV_CACHE(v_cache);
-  TORCH_CHECK(k_cache.dim() == 4 && v_cache.sizes() == k_cache.sizes() &&
-                  v_cache.scalar_type() == k_cache.scalar_type(),
-              "attn_prefill_paged_split: k_cache/v_cache must be [NB, KVH, BS, D] of one dtype");
-  const int T = q.size(0), H = q.size(1), D = q.size(2);
-  const int KVH = k_cache.size(1), BS = k_cache.size(2);
-  TORCH_CHECK(D == 128 && k_cache.size(3) == 128, "attn_prefill_paged_split: head_dim must be 128");
-  TORCH_CHECK(KVH > 0 && H % KVH == 0, "attn_prefill_paged_split: H must be a multiple of KVH");
-  TORCH_CHECK(out.dim() == 3 && out.sizes() == q.sizes(),
-              "attn_prefill_paged_split: out must be [T, H, D]");
-  TORCH_CHECK(q.stride(0) >= (int64_t)H * D && q.stride(0) % 8 == 0 &&
-                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
-              "attn_prefill_paged_split: q token stride must cover H*D and keep rows 16-byte aligned");
-  auto ok = [](const torch::Tensor& t) {
-    return t.is_cuda() && t.is_contiguous() && t.scalar_type() == at::kInt;
-  };
-  TORCH_CHECK(ok(block_tables) && ok(cu_q) && ok(q_start) && ok(grp_seq) && ok(grp_qpos0) &&
-                  ok(grp_krange) && ok(grp_split) && ok(seq_nsplit) && ok(seq_ws_base),
-              "attn_prefill_paged_split: metadata must be contiguous int32 on GPU");
-  const int n_seq = q_start.numel();
-  TORCH_CHECK(n_seq >= 1 && cu_q.numel() == n_seq + 1, "cu_q must be [n_seq + 1]");
-  TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(0) == n_seq && block_tables.size(1) >= 1,
-              "block_tables must be [n_seq, max_blocks]");
-  const int n_groups = grp_seq.numel();
-  TORCH_CHECK(grp_qpos0.numel() == (int64_t)n_groups * 8, "grp_qpos0 must be [G*8]");
-  TORCH_CHECK(grp_krange.numel() == (int64_t)n_groups * 2, "grp_krange must be [G*2]");
-  TORCH_CHECK(grp_split.numel() == n_groups, "grp_split must be [G]");
-  TORCH_CHECK(seq_nsplit.numel() == n_seq && seq_ws_base.numel() == n_seq,
+  const PagedPrefillDims d = check_paged_prefill(
+      "attn_prefill_paged_split", out, q, k_cache, v_cache, block_tables, cu_q, q_start,
+      grp_seq, grp_qpos0, k_scale, v_scale, {grp_krange, grp_split, seq_nsplit, seq_ws_base});
+  TORCH_CHECK(grp_krange.numel() == (int64_t)d.n_groups * 2, "grp_krange must be [G*2]");
+  TORCH_CHECK(grp_split.numel() == d.n_groups, "grp_split must be [G]");
+  TORCH_CHECK(seq_nsplit.numel() == d.n_seq && seq_ws_base.numel() == d.n_seq,
               "seq_nsplit and seq_ws_base must be [n_seq]");
   TORCH_CHECK(max_splits >= 2 && max_splits <= 64,
               "attn_prefill_paged_split: max_splits must be 2..64");
-  TORCH_CHECK(ws_rows >= 1 && ws_rows <= (int64_t)T * max_splits,
+  TORCH_CHECK(ws_rows >= 1 && ws_rows <= (int64_t)d.T * max_splits,
               "attn_prefill_paged_split: ws_rows must be 1..T*max_splits");
   auto ws_ok = [&](const torch::Tensor& t, int64_t last) {
     return t.is_cuda() && t.is_contiguous() && t.scalar_type() == at::kFloat && t.dim() == 3 &&
-           t.size(0) >= ws_rows && t.size(1) == H && t.size(2) == last &&
+           t.size(0) >= ws_rows && t.size(1) == d.H && t.size(2) == last &&
            reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
   };
   TORCH_CHECK(ws_ok(part_o, 128) && ws_ok(part_ml, 2),
               "attn_prefill_paged_split: part_o / part_ml must be contiguous fp32 "
               "[>= ws_rows, H, 128] / [>= ws_rows, H, 2]");
-  const int cache_fp8 = k_cache.scalar_type() == at::kFloat8_e4m3fn ? 1 : 0;
-  if (cache_fp8) {
-    TORCH_CHECK(k_scale.is_cuda() && v_scale.is_cuda() &&
-                    k_scale.numel() == k_cache.size(0) * KVH * BS && k_scale.is_contiguous() &&
-                    v_scale.is_contiguous() && k_scale.scalar_type() == at::kFloat &&
-                    v_scale.scalar_type() == at::kFloat && v_scale.numel() == k_scale.numel(),
-                "fp8 attn_prefill_paged_split requires [NB, KVH, BS] fp32 k_scale/v_scale");
-  } else {
-    TORCH_CHECK(k_scale.numel() == 0 && v_scale.numel() == 0,
-                "attn_prefill_paged_split: k_scale/v_scale go with fp8 caches only");
-  }
-  if (T == 0 || n_groups == 0) return;
+  if (d.T == 0 || d.n_groups == 0) return;
   launch_attn_prefill_paged_split(
       bf(out), cbf(q), k_cache.data_ptr(), v_cache.data_ptr(),
-      cache_fp8 ? k_scale.data_ptr<float>() : nullptr,
-      cache_fp8 ? v_scale.data_ptr<float>() : nullptr,
+      d.cache_fp8 ? k_scale.data_ptr<float>() : nullptr,
+      d.cache_fp8 ? v_scale.data_ptr<float>() : nullptr,
       block_tables.data_ptr<int>(), cu_q.data_ptr<int>(), q_start.data_ptr<int>(),
       grp_seq.data_ptr<int>(), grp_qpos0.data_ptr<int>(), grp_krange.data_ptr<int>(),
       grp_split.data_ptr<int>(), seq_nsplit.data_ptr<int>(), seq_ws_base.data_ptr<int>(),
       part_o.data_ptr<float>(), part_ml.data_ptr<float>(), (int)ws_rows, (int)max_splits,
-      (float)scale, n_seq, T, H, KVH, (int)k_cache.size(0), BS, (int)block_tables.size(1),
-      (int)q.stride(0), n_groups, cache_fp8, cur_stream());
+      (float)scale, d.n_seq, d.T, d.H, d.KVH, (int)k_cache.size(0), d.BS,
+      (int)block_tables.size(1), (int)q.stride(0), d.n_groups, d.cache_fp8, cur_stream());
 }
 
 void sample(torch::Tensor tokens, torch::Tensor logprobs, torch::Tensor logits,
