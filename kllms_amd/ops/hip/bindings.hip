@@ -535,18 +535,35 @@ static const float* moe_weight_scale(const torch::Tensor& w, const torch::Tensor
   return scale.data_ptr<float>();
 }
 
+// sorted_ids / pad_offsets: contiguous 1-D int32 on the GPU
+static void check_moe_routing(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.dim() == 1 && t.scalar_type() == at::kInt,
+              name, " must be a contiguous 1-D int32 tensor on GPU");
+}
+
+// the kernels take raw pointers: every operand lives on the output's device
+// (an empty tensor, the "no scales" placeholder, has no memory to be read)
+static void check_moe_one_device(const torch::Tensor& out, std::initializer_list<torch::Tensor> ts) {
+  for (const auto& t : ts)
+    TORCH_CHECK(t.numel() == 0 || t.device() == out.device(),
+                "grouped MoE operands must be on one device");
+}
+
 void moe_gateup(torch::Tensor act, torch::Tensor x, torch::Tensor w, torch::Tensor scale,
                 torch::Tensor sorted_ids, torch::Tensor pad_offsets, torch::Tensor zeros) {
   CHECK_BF16_CONTIG(act); CHECK_BF16_CONTIG(x); CHECK_BF16_CONTIG(zeros);
+  TORCH_CHECK(act.dim() == 2 && x.dim() == 2, "act and x must be 2-D");
   const float* sc = moe_weight_scale(w, scale);
-  TORCH_CHECK(sorted_ids.scalar_type() == at::kInt && pad_offsets.scalar_type() == at::kInt,
-              "routing tensors must be int32");
+  check_moe_routing(sorted_ids, "sorted_ids");
+  check_moe_routing(pad_offsets, "pad_offsets");
+  check_moe_one_device(act, {x, w, scale, zeros, sorted_ids, pad_offsets});
   const int E = w.size(0);
   const int IN = w.size(1) / 2;
   const int K = w.size(2);
   TORCH_CHECK(IN % 64 == 0 && K % 64 == 0, "IN % 64, K % 64 required");
   TORCH_CHECK(act.size(1) == IN && x.size(1) == K && zeros.numel() >= K);
   TORCH_CHECK(act.size(0) % 128 == 0, "sorted rows must be padded to 128");
+  TORCH_CHECK(sorted_ids.numel() == act.size(0), "sorted_ids must have one entry per row of act");
   TORCH_CHECK(pad_offsets.numel() == E + 1);
   launch_moe_gateup(act.data_ptr(), x.data_ptr(), w.data_ptr(), sc,
                     sorted_ids.data_ptr<int>(), pad_offsets.data_ptr<int>(),
@@ -556,12 +573,17 @@ void moe_gateup(torch::Tensor act, torch::Tensor x, torch::Tensor w, torch::Tens
 void moe_down(torch::Tensor y, torch::Tensor act, torch::Tensor w, torch::Tensor scale,
               torch::Tensor pad_offsets) {
   CHECK_BF16_CONTIG(y); CHECK_BF16_CONTIG(act);
+  TORCH_CHECK(y.dim() == 2 && act.dim() == 2, "y and act must be 2-D");
   const float* sc = moe_weight_scale(w, scale);
+  check_moe_routing(pad_offsets, "pad_offsets");
+  check_moe_one_device(y, {act, w, scale, pad_offsets});
   const int E = w.size(0);
   const int H = w.size(1);
   const int IN = w.size(2);
   TORCH_CHECK(H % 64 == 0 && IN % 64 == 0, "H % 64, IN % 64 required");
   TORCH_CHECK(y.size(1) == H && act.size(1) == IN);
+  TORCH_CHECK(y.size(0) == act.size(0), "y and act must have the same sorted rows");
+  TORCH_CHECK(y.size(0) % 128 == 0, "sorted rows must be padded to 128");
   TORCH_CHECK(pad_offsets.numel() == E + 1);
   launch_moe_down(y.data_ptr(), act.data_ptr(), w.data_ptr(), sc,
                   pad_offsets.data_ptr<int>(), E, H, IN, cur_stream());
