@@ -22,6 +22,7 @@ blocks return at once, no chunk is skipped).
 
 from __future__ import annotations
 
+import gc
 from typing import Dict, List, Optional
 
 import torch
@@ -85,9 +86,23 @@ class DecodeGraphRunner:
         # under capture rocBLAS picks a stream-K algorithm (~3x slower, plus a
         # workspace fill) for the [B,H]x[H,V] shape; eager picks the
         # weight-streaming-bound one (measured in scripts/lmhead_probe.py).
+        #
+        # No cyclic garbage collection while the stream is capturing: an engine
+        # and its graph runner refer to each other, so a dead engine's hipGraphs,
+        # streams and GPU memory are released only by the collector, and
+        # releasing them in the middle of a capture is not allowed (it has
+        # aborted the process). torch.cuda.graph no longer collects before it
+        # captures, so do it here, then hold the collector off until the end.
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            out = eng.model.forward_hidden(buf["ids"], batch)
+        gc.collect()
+        gc_was_enabled = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(g):
+                out = eng.model.forward_hidden(buf["ids"], batch)
+        finally:
+            if gc_was_enabled:
+                gc.enable()
         buf["out"] = out
         self.graphs[bs] = g
         self.buffers[bs] = buf

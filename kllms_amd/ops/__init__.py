@@ -48,6 +48,11 @@ def _hip_or_raise():
     return _C
 
 
+def _scale_or_empty(scale: Optional[torch.Tensor], device: torch.device) -> torch.Tensor:
+    """The binding takes an empty tensor for 'bf16 weights or caches, no scales'."""
+    return scale if scale is not None else torch.empty(0, dtype=torch.float32, device=device)
+
+
 def rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float) -> torch.Tensor:
     if x.is_cuda and not _force_torch():
         out = torch.empty_like(x)
@@ -179,11 +184,9 @@ def store_kv(
     """k_scale/v_scale: [NB, KVH, BS] fp32 per-row dequant scales, REQUIRED
     when the caches are fp8 (written here: s = amax(|row|)/448), None for bf16."""
     if k.is_cuda and not _force_torch():
-        none = torch.empty(0, dtype=torch.float32, device=k.device)
         _hip_or_raise().store_kv(
             k, v, k_cache, v_cache, slot_mapping,
-            k_scale if k_scale is not None else none,
-            v_scale if v_scale is not None else none)
+            _scale_or_empty(k_scale, k.device), _scale_or_empty(v_scale, k.device))
         return
     torch_ref.store_kv(k, v, k_cache, v_cache, slot_mapping, k_scale, v_scale)
 
@@ -205,11 +208,9 @@ def rope_store_kv(
     untouched v go to the paged caches at ``slot_mapping``. q, k, both caches
     and (fp8) both scale arrays end up with the bits of the two separate ops."""
     if q.is_cuda and not _force_torch():
-        none = torch.empty(0, dtype=torch.float32, device=q.device)
         _hip_or_raise().rope_store_kv(
             q, k, v, positions, cos_sin, k_cache, v_cache, slot_mapping,
-            k_scale if k_scale is not None else none,
-            v_scale if v_scale is not None else none)
+            _scale_or_empty(k_scale, q.device), _scale_or_empty(v_scale, q.device))
         return
     torch_ref.rope_inplace(q, k, positions, cos_sin)
     torch_ref.store_kv(k, v, k_cache, v_cache, slot_mapping, k_scale, v_scale)
@@ -298,9 +299,7 @@ def attn_decode_paged(
     kernel covers the rest. ``None`` is the per-stream path alone."""
     if q.is_cuda and not _force_torch():
         out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
-        none = torch.empty(0, dtype=torch.float32, device=q.device)
-        ks = k_scale if k_scale is not None else none
-        vs = v_scale if v_scale is not None else none
+        ks, vs = _scale_or_empty(k_scale, q.device), _scale_or_empty(v_scale, q.device)
         if shared is None:
             _hip_or_raise().attn_decode_paged(
                 out, q, k_cache, v_cache, block_tables, context_lens, scale, ks, vs)
@@ -533,9 +532,7 @@ def attn_prefill_paged(
     elsewhere ``torch_ref.attn_prefill_paged_split`` walks the same plan."""
     if q.is_cuda and not _force_torch():
         out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
-        none = torch.empty(0, dtype=torch.float32, device=q.device)
-        ks = k_scale if k_scale is not None else none
-        vs = v_scale if v_scale is not None else none
+        ks, vs = _scale_or_empty(k_scale, q.device), _scale_or_empty(v_scale, q.device)
         if meta.has_splits:
             H = q.shape[1]
             part_o = torch.empty((meta.ws_rows, H, 128), dtype=torch.float32, device=q.device)
@@ -634,11 +631,6 @@ def sample_fsm(
         return tokens, logprobs
     return torch_ref.sample_fsm(logits, temperatures, top_ps, top_ks, seeds, steps,
                                 fsm_state, tables)
-
-
-def _scale_or_empty(scale: Optional[torch.Tensor], device: torch.device) -> torch.Tensor:
-    """The binding takes an empty tensor for 'bf16 weights, no scales'."""
-    return scale if scale is not None else torch.empty(0, dtype=torch.float32, device=device)
 
 
 def moe_gateup(

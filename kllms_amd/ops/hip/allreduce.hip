@@ -23,7 +23,7 @@
 // Reference parity note: the reference has no collectives (its backend is a
 // remote API); this accelerates the native TP path only.
 
-#include "common.h"
+#include "launch.h"
 
 #include <cstdio>
 #include <cstring>

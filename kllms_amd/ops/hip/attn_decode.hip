@@ -42,7 +42,7 @@
 // Layouts: q [B, H, D=128]; caches [NB, KVH, BS, D]; block_tables [B, MAXB];
 // context_lens INCLUDE the current token. GQA in {1, 2, 4, 8}.
 
-#include "common.h"
+#include "launch.h"
 
 #include <type_traits>
 
@@ -52,7 +52,7 @@
 // chunk size is a runtime arg (adaptive split-K: big batches need no split)
 
 // partials layout: [B, KVH, max_chunks, gqa, 130]: 128 o values + m + l
-#define PART_STRIDE 130
+#define PART_STRIDE ATTN_DECODE_PART_STRIDE
 #define V_GROUP 16         // V keys a wave keeps in flight per load group
 
 static_assert(TKV == NTHREADS, "one rowoff slot per thread");
@@ -380,7 +380,7 @@ extern "C" void launch_attn_decode_partial(
     case 2: DISPATCH(2); break;
     case 4: DISPATCH(4); break;
     case 8: DISPATCH(8); break;
-    default: DISPATCH(8); break;  // guarded by the binding's gqa<=8 check
+    default: DISPATCH(8); break;  // not reached: launch.h limits H / KVH to {1, 2, 4, 8}
   }
 #undef DISPATCH
 #undef LAUNCH
@@ -420,4 +420,13 @@ extern "C" __global__ void __launch_bounds__(64) attn_decode_reduce_kernel(
   const uint32_t pair = ((uint32_t)(uint16_t)f32_to_bf16(acc1 * inv_l) << 16) |
                         (uint16_t)f32_to_bf16(acc0 * inv_l);
   *reinterpret_cast<uint32_t*>((short*)op + lane * 2) = pair;
+}
+
+extern "C" void launch_attn_decode_reduce(bf16_t* out, const float* partials,
+                                          const int* context_lens, int B, int num_q_heads,
+                                          int num_kv_heads, int max_chunks, int chunk_keys,
+                                          hipStream_t stream) {
+  hipLaunchKernelGGL(attn_decode_reduce_kernel, dim3(B, num_q_heads), dim3(WAVE), 0, stream,
+                     out, partials, context_lens, num_q_heads, num_kv_heads, max_chunks,
+                     chunk_keys);
 }

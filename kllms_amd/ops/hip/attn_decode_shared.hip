@@ -27,13 +27,14 @@
 // end.
 
 #include "attn_mfma.h"
+#include "launch.h"
 
 #define SP_THREADS 256
 #define SP_TILE_ROWS 64            // query rows per tile (2 MFMA row blocks)
 #define SP_ROUND_KEYS 128          // keys staged per barrier round (32 per wave)
 #define SP_VT_ROW 136              // shorts: 128 keys + 8 pad (conflict-free b128 reads)
 #define SP_O_STRIDE 132            // floats per merged-o row (16B-aligned rows)
-#define SP_PART_STRIDE 130
+#define SP_PART_STRIDE ATTN_DECODE_PART_STRIDE
 
 #define SP_STAGE_BYTES (SP_ROUND_KEYS * ATTN_K_ROW_BYTES + 128 * SP_VT_ROW * 2)   // 67584
 #define SP_MERGE_BYTES (4 * 32 * SP_O_STRIDE * 4)                              // 67584

@@ -12,6 +12,7 @@
 // block PER SEQUENCE; grp_qpos0 = -1 pads idle waves.
 
 #include "attn_mfma.h"
+#include "launch.h"
 
 #define QBLK 32
 #define KVBLK 64                   // staged keys per barrier round (2 MFMA sub-tiles)
@@ -125,4 +126,14 @@ extern "C" __global__ void __launch_bounds__(64 * NWAVES) attn_prefill_kernel(
 #pragma unroll
       for (int g2 = 0; g2 < 4; ++g2) store_o_bf16(op, o_acc[dt], inv_l, dt, g2, half);
   }
+}
+
+extern "C" void launch_attn_prefill(bf16_t* out, const bf16_t* q, const bf16_t* k, const bf16_t* v,
+                                    const int* grp_seq_start, const int* grp_seqlen,
+                                    const int* grp_qpos0, float scale, int n_groups,
+                                    int num_q_heads, int num_kv_heads, int q_tstride,
+                                    int kv_tstride, hipStream_t stream) {
+  hipLaunchKernelGGL(attn_prefill_kernel, dim3(n_groups, num_q_heads), dim3(64 * NWAVES), 0,
+                     stream, out, q, k, v, grp_seq_start, grp_seqlen, grp_qpos0, scale,
+                     num_q_heads, num_kv_heads, q_tstride, kv_tstride);
 }

@@ -39,6 +39,7 @@
 // kend, the split index and the slot are clamped like the rest.
 
 #include "attn_mfma.h"
+#include "launch.h"
 
 typedef float pp_f32x2 __attribute__((ext_vector_type(2)));
 

@@ -6,7 +6,9 @@
 // RoPE precomputed on host — Appendix B: on-device trig turns memory-bound
 // into VALU-bound).
 
-#include "common.h"
+#include "launch.h"
+
+#include <algorithm>
 
 // --------------------------------------------------------------------------
 // RMSNorm: one block per row, row length N (multiple of 8), bf16 in/out.
@@ -412,4 +414,82 @@ extern "C" __global__ void __launch_bounds__(256) rope_store_kv_fp8_kernel(
   rope_store_kv_body<true>(q, k, v, k_cache, v_cache, k_scale, v_scale, positions, cos_sin,
                            slots, num_q_heads, num_kv_heads, head_dim, block_size,
                            q_tstride, k_tstride, v_tstride);
+}
+
+// --------------------------------------------------------------------------
+// Host-side launchers (contracts in launch.h). The grid-stride kernels cap
+// their grid at ELEM_MAX_GRID blocks (G11).
+// --------------------------------------------------------------------------
+#define ELEM_THREADS 256
+#define ELEM_MAX_GRID 2048
+#define ROWS_PER_BLOCK (ELEM_THREADS / WAVE)   // one wave per row: blockIdx * 4 + (threadIdx >> 6)
+
+static int capped_grid(int64_t work_items, int per_block) {
+  return (int)std::min<int64_t>((work_items + per_block - 1) / per_block, ELEM_MAX_GRID);
+}
+
+extern "C" void launch_rmsnorm(bf16_t* out, const bf16_t* in, const bf16_t* w, int rows, int n,
+                               float eps, hipStream_t stream) {
+  hipLaunchKernelGGL(rmsnorm_kernel, dim3(rows), dim3(ELEM_THREADS), 0, stream, out, in, w, n, eps);
+}
+
+extern "C" void launch_fused_add_rmsnorm(bf16_t* out, const bf16_t* x, bf16_t* residual,
+                                         const bf16_t* w, int rows, int n, float eps,
+                                         hipStream_t stream) {
+  hipLaunchKernelGGL(fused_add_rmsnorm_kernel, dim3(rows), dim3(ELEM_THREADS), 0, stream,
+                     out, x, residual, w, n, eps);
+}
+
+extern "C" void launch_silu_mul(bf16_t* out, const bf16_t* gate, const bf16_t* up, int64_t rows,
+                                int64_t ncols, int64_t row_stride, hipStream_t stream) {
+  const int64_t nvec = rows * ncols / 8;
+  hipLaunchKernelGGL(silu_mul_kernel, dim3(capped_grid(nvec, ELEM_THREADS)), dim3(ELEM_THREADS),
+                     0, stream, out, gate, up, nvec, (int)(ncols / 8), (int)(row_stride / 8));
+}
+
+extern "C" void launch_rope(bf16_t* q, bf16_t* k, const int64_t* positions, const float* cos_sin,
+                            int T, int num_q_heads, int num_kv_heads, int head_dim,
+                            int q_tstride, int k_tstride, hipStream_t stream) {
+  // one lane per rotation pair
+  hipLaunchKernelGGL(rope_kernel, dim3(T, num_q_heads + num_kv_heads), dim3(head_dim / 2), 0,
+                     stream, q, k, positions, cos_sin, num_q_heads, num_kv_heads, head_dim,
+                     q_tstride, k_tstride);
+}
+
+extern "C" void launch_store_kv(const bf16_t* k, const bf16_t* v, void* k_cache, void* v_cache,
+                                float* k_scale, float* v_scale, const int64_t* slots, int T,
+                                int num_kv_heads, int head_dim, int block_size, int kv_tstride,
+                                int cache_fp8, hipStream_t stream) {
+  if (cache_fp8) {
+    // per-row quantization: one wave per (token, head) row
+    const int grid = capped_grid((int64_t)T * num_kv_heads, ROWS_PER_BLOCK);
+    hipLaunchKernelGGL(store_kv_fp8_kernel, dim3(grid), dim3(ELEM_THREADS), 0, stream, k, v,
+                       (unsigned char*)k_cache, (unsigned char*)v_cache, k_scale, v_scale, slots,
+                       T, num_kv_heads, head_dim, block_size, kv_tstride);
+  } else {
+    const int grid = capped_grid((int64_t)T * num_kv_heads * (head_dim / 8), ELEM_THREADS);
+    hipLaunchKernelGGL(store_kv_kernel, dim3(grid), dim3(ELEM_THREADS), 0, stream, k, v,
+                       (bf16_t*)k_cache, (bf16_t*)v_cache, slots, T, num_kv_heads, head_dim,
+                       block_size, kv_tstride);
+  }
+}
+
+extern "C" void launch_rope_store_kv(bf16_t* q, bf16_t* k, const bf16_t* v, void* k_cache,
+                                     void* v_cache, float* k_scale, float* v_scale,
+                                     const int64_t* positions, const float* cos_sin,
+                                     const int64_t* slots, int T, int num_q_heads,
+                                     int num_kv_heads, int head_dim, int block_size,
+                                     int q_tstride, int k_tstride, int v_tstride, int cache_fp8,
+                                     hipStream_t stream) {
+  const dim3 grid(T, (num_q_heads + num_kv_heads + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
+  if (cache_fp8)
+    hipLaunchKernelGGL(rope_store_kv_fp8_kernel, grid, dim3(ELEM_THREADS), 0, stream, q, k, v,
+                       (unsigned char*)k_cache, (unsigned char*)v_cache, k_scale, v_scale,
+                       positions, cos_sin, slots, num_q_heads, num_kv_heads, head_dim,
+                       block_size, q_tstride, k_tstride, v_tstride);
+  else
+    hipLaunchKernelGGL(rope_store_kv_kernel, grid, dim3(ELEM_THREADS), 0, stream, q, k, v,
+                       (bf16_t*)k_cache, (bf16_t*)v_cache, positions, cos_sin, slots,
+                       num_q_heads, num_kv_heads, head_dim, block_size, q_tstride, k_tstride,
+                       v_tstride);
 }

@@ -11,7 +11,7 @@
 // One source may feed many destinations; the host guarantees that no block is
 // both a source and a destination of the same call, so units never race.
 
-#include "common.h"
+#include "launch.h"
 
 #define KV_COPY_MAX_GRID 2048
 

@@ -14,7 +14,7 @@
 // Grid-stride over pairs; each pair reads two <=64-byte rows of the packed
 // [N, 64] char matrix. 100k pairs ~ a few hundred us.
 
-#include "common.h"
+#include "launch.h"
 
 extern "C" __global__ void levenshtein_kernel(
     int* __restrict__ out_dist,          // [P]

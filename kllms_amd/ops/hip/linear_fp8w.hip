@@ -44,7 +44,7 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "launch.h"
 
 #define FW_BK 64                 // k per stage: 128 B of x per row, 64 B of weight
 #define FW_BN 128                // output columns per block (4 waves x 32)

@@ -8,7 +8,7 @@
 //   B[k][j]: j = l&31, k = (l>>5)*8 + jj
 //   D[i][j]: j = l&31, i = (r&3) + 8*(r>>2) + 4*(l>>5)   (r = 0..15)
 
-#include "common.h"
+#include "launch.h"
 
 typedef __bf16 bf16x8_mfma __attribute__((ext_vector_type(8)));
 
@@ -34,4 +34,9 @@ extern "C" __global__ void __launch_bounds__(64) mfma_selftest_kernel(
     const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
     D[row * 32 + col] = acc[r];
   }
+}
+
+extern "C" void launch_mfma_selftest(float* D, const bf16_t* A, const bf16_t* B,
+                                     hipStream_t stream) {
+  hipLaunchKernelGGL(mfma_selftest_kernel, dim3(1), dim3(WAVE), 0, stream, D, A, B);
 }

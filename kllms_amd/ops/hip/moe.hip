@@ -31,7 +31,7 @@
 // common.h) on its way into the SAME swizzled bf16 LDS tile, so the MFMA loop
 // is shared, and the scales multiply the fp32 accumulators in the epilogue.
 
-#include "common.h"
+#include "launch.h"
 
 #define MOE_BM 128
 #define MOE_BN 64

@@ -20,7 +20,7 @@
 //
 // temperature == 0 -> greedy (argmax + logprob only).
 
-#include "common.h"
+#include "launch.h"
 
 // sx(x) must be BIT-IDENTICAL across pass B (histogram), pass C's
 // refinement rescans and pass D (admission). hipcc contracts even
@@ -394,4 +394,25 @@ extern "C" __global__ void __launch_bounds__(NT) sample_fsm_kernel(
     }
     fsm_state[b] = ns;
   }
+}
+
+// per-wave histograms of sample_row: hist_mass then hist_cnt, [NW][SBINS] each
+#define SAMPLE_LDS_BYTES (NW * SBINS * (sizeof(float) + sizeof(unsigned int)))
+
+extern "C" void launch_sample(int64_t* tokens, float* logprobs, const float* logits,
+                              const float* temperatures, const float* top_ps, const int* top_ks,
+                              const int64_t* seeds, const int64_t* steps, const uint32_t* mask,
+                              int B, int V, float* dbg, hipStream_t stream) {
+  hipLaunchKernelGGL(sample_kernel, dim3(B), dim3(NT), SAMPLE_LDS_BYTES, stream, tokens,
+                     logprobs, logits, temperatures, top_ps, top_ks, seeds, steps, mask, V, dbg);
+}
+
+extern "C" void launch_sample_fsm(int64_t* tokens, float* logprobs, const float* logits,
+                                  const float* temperatures, const float* top_ps,
+                                  const int* top_ks, const int64_t* seeds, const int64_t* steps,
+                                  int32_t* fsm_state, const int64_t* tabs, int eos_id, int B,
+                                  int V, hipStream_t stream) {
+  hipLaunchKernelGGL(sample_fsm_kernel, dim3(B), dim3(NT), SAMPLE_LDS_BYTES, stream, tokens,
+                     logprobs, logits, temperatures, top_ps, top_ks, seeds, steps, fsm_state,
+                     tabs, eos_id, V);
 }

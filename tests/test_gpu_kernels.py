@@ -466,6 +466,41 @@ class TestEngineGPU:
         t = torch.randn(64, device=DEV)  # generator must serve RNG again
         assert torch.isfinite(t).all()
 
+    def test_no_garbage_collection_while_capturing(self):
+        """The cyclic collector is off while the decode step is captured (a
+        dead engine's hipGraphs and GPU memory must not be released inside a
+        capture; see DecodeGraphRunner._capture) and back on afterwards. The
+        test only reads the collector's state from inside an ordinary capture."""
+        import gc
+
+        from kllms_amd.engine.config import EngineConfig
+        from kllms_amd.engine.engine import GenRequest, LLMEngine
+        from kllms_amd.engine.sampling import SamplingParams
+
+        assert gc.isenabled()
+        eng = LLMEngine(EngineConfig(
+            model="mid-llama", max_kv_blocks=256, use_hip_graphs=True,
+            hip_graph_batch_sizes=[1, 2, 4], max_seq_len=512, seed=12,
+        ))
+        orig = eng.model.forward_hidden
+        seen = []
+
+        def watched(ids, batch):
+            if torch.cuda.is_current_stream_capturing():
+                seen.append(gc.isenabled())
+            return orig(ids, batch)
+
+        eng.model.forward_hidden = watched
+        try:
+            eng.generate([GenRequest(
+                prompt_ids=list(range(1, 20)), n=2,
+                sampling=SamplingParams(temperature=0.0, max_tokens=4))])
+        finally:
+            eng.model.forward_hidden = orig
+        assert seen and not any(seen), "the collector was enabled during capture"
+        assert gc.isenabled(), "the collector was left disabled"
+        assert eng._graph_runner._enabled
+
 
 class TestFp8KVCacheGPU:
     def test_store_and_decode_fp8(self):
